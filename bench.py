@@ -12,9 +12,16 @@ Score mode: `exact` by default -- fp32 Gaussian, every pbest / gbest comparison 
 fp64: the poses (and costs) of the all-fp64 mode, which are the oracle's, bit for bit (tests/test_gpu_fullsize.py
 checks all 512 pairs of this very workload).  `--score f32` is the plain fp32 score (BASELINE config 2's "fp32":
 a tolerance mode, 1 of 4096 pairs leaves the reference's trajectory), `--score f64` the fp64 score throughout;
-both are timed as `extra.modes` of the default run.
+both are timed as `extra.modes` of a `--full` run.
 
-Prints ONE JSON line on rank 0 (contract in the task statement), with
+A plain run (`bench.py --gpus 1 --steps N --warmup W`) does what the headline needs and no more: set-up, clock settle, W warm-up
+steps, the N timed steps, the result line.  `--dump-outputs DIR` adds `DIR/{pose,cost,status,n_points}.npy` (float64): what the last
+timed step computed, for the same arguments the same inputs in every run.  `--full` adds every measurement that takes runs of
+its own -- the figure without clock settle, one batch at a time (the per-launch duration and the roofline's per-launch figures:
+null in a plain run with two batches in flight), the duration of the RCCL gather, the other score modes, config 5, short scans,
+single-pair latency, the live sequences, the CPU baseline with its parity figure -- as it always did; minutes instead of seconds.
+
+Prints ONE JSON line on rank 0, with
   roofline      bound "valu": the kernel keeps table, points and swarm in LDS, HBM sees 8.7 KB per alignment; what
                 bounds it is the chip's vector ALU.  achieved = SURVEY 8(d)'s flops per point evaluation (16 fp64 + 34
                 fp32 + 1 exp) x the algorithmic point evaluations of a launch / the launch's duration (events, one
@@ -25,7 +32,7 @@ Prints ONE JSON line on rank 0 (contract in the task statement), with
   value         steps / time with two batches in flight in the one context (ndtpso_set_pipeline_depth(2): step k + 1 is
                 launched while step k's slowest alignments finish); extra.batches_in_flight.one_batch_at_a_time is the
                 figure of rounds 1-2 (--pipeline 1 makes it the headline).
-  cpu_baseline  the oracle (a port of the reference's algorithm) on this box's host cores, SURVEY 8(d)'s four numbers.
+  cpu_baseline  (--full) the oracle (a port of the reference's algorithm) on the host's cores, SURVEY 8(d)'s four numbers.
   clock settle  a process that has just started finds the device in a low power state: before the `warmup` steps the same launches
                 run, untimed, for --settle-ms of wall time (default 400; extra.clock_settle says how many), and again before the
                 one-at-a-time measurement that follows the timed region.  The timed region itself is exactly `steps` steps.
@@ -65,8 +72,13 @@ def main():
     ap.add_argument("--pipeline", type=int, choices=[1, 2], default=2,
                     help="batches in flight in the context (ndtpso_set_pipeline_depth): 2 = step k + 1 is launched while step k's "
                          "slowest alignments finish (the default, what a caller with a queue of batches does); 1 = one at a time")
-    ap.add_argument("--cpu-sample", type=int, default=512, help="pairs of this step timed on the host oracle (0 = skip the CPU baseline)")
-    ap.add_argument("--no-latency", action="store_true", help="skip the extras (other score modes, config 5, latency, live sequence)")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline: the measurement without clock settle, one batch at a time (per-launch roofline figures), "
+                         "the duration of the RCCL gather, the extras and the CPU baseline -- runs of their own, minutes; off by default")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the last of them computed (pose, cost, status of every pair) as DIR/<name>.npy")
+    ap.add_argument("--cpu-sample", type=int, default=512, help="with --full: pairs of this step timed on the host oracle (0 = skip the CPU baseline)")
+    ap.add_argument("--no-latency", action="store_true", help="with --full: skip the extras (other score modes, config 5, latency, live sequence)")
     ap.add_argument("--identical", action="store_true", help="diagnostic: replicate pair 0 (no load imbalance)")
     ap.add_argument("--sharded-capi", action="store_true",
                     help="ONE process driving --gpus N devices through the C-ABI's ndtpso_align_pairs_sharded_dev (a host thread, "
@@ -84,8 +96,10 @@ def main():
         raise SystemExit(2)
     if kind == "relaunch":
         print("bench.py: --gpus %d without a launcher: starting %s" % (args.gpus, " ".join(detail)), file=sys.stderr, flush=True)
-        os.environ["NDTPSO_BENCH_SELF_LAUNCHED"] = "1"
-        os.execv(detail[0], detail)
+        # (a child process, not an exec: counting the devices above has initialised the GPU runtime in this process, and a process
+        # in that state must not replace its own program)
+        import subprocess
+        raise SystemExit(subprocess.run(detail, env=dict(os.environ, NDTPSO_BENCH_SELF_LAUNCHED="1")).returncode)
 
     # stdout carries exactly one line, the JSON result: everything else that may print there on the way (RCCL's
     # version banner, device-side printf of diagnostic builds) is sent to stderr at the file-descriptor level
@@ -183,7 +197,7 @@ def main():
     # Before it, once: what rounds 1-4 measured -- `warmup` + `steps` launches at the configured depth straight after start-up,
     # then min(steps, 60) one at a time -- so that the driver's line stays comparable across rounds (extra.without_clock_settle).
     cold = None
-    if args.settle_ms > 0 and world == 1:
+    if args.full and args.settle_ms > 0 and world == 1:
         cold = {}
         for k in range(args.warmup):
             launch(k)
@@ -241,16 +255,22 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
     ctx.synchronize()
+    # what the last timed step wrote (a copy: the measurements of --full that follow launch into the same buffers)
+    last_pose, last_cost, last_stats = (t.cpu().numpy() for t in (outs[(args.steps - 1) & 1] if depth > 1 and args.steps > 0 else outs[0]))
     poses_equal_between_sets = bool(torch.equal(outs[0][0], outs[1][0])) if depth > 1 and args.steps > 1 else None
+    if args.dump_outputs and rank == 0 and not use_dist:
+        _dump_outputs(args.dump_outputs, capi, last_pose, last_cost, last_stats)
 
     # Per-launch duration of the kernel, one launch at a time (events on the launch stream): what the rocprofv3 kernel
     # trace of `bench.py --pipeline 1` averages, and what the roofline divides by.  With two batches in flight a
     # launch's own duration says nothing (two launches share the device); the serial figure is measured here, after
-    # the timed region, over min(steps, 60) launches.
+    # the timed region, over min(steps, 60) launches -- a run of its own, so with --full only (null otherwise).
     ctx.set_pipeline_depth(1)
     if depth == 1:
         kern_ms = float(np.mean([a.elapsed_time(b) for a, b in ev])) if args.steps else float("nan")
         serial_ms = 1e3 * elapsed / max(args.steps, 1)
+    elif not args.full:
+        kern_ms = serial_ms = None
     else:
         ns = max(1, min(args.steps, 60))
         evs = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(ns)]
@@ -275,12 +295,12 @@ def main():
         serial_ms = 1e3 * (time.perf_counter() - t1) / ns
         kern_ms = float(np.mean([a.elapsed_time(b) for a, b in evs]))
 
-    stats = d_stats.cpu().numpy().view(capi.STATS_DTYPE).reshape(B)
-    pose = d_pose.cpu().numpy()
+    stats = last_stats.view(capi.STATS_DTYPE).reshape(B)
+    pose = last_pose
     n_valid = stats["n_points"].astype(np.float64)
     evals_nominal = 1 + P + P * I                      # cost evaluations the reference performs per alignment
     algo_bytes = float(n_valid.sum()) * evals_nominal * BYTES_PER_POINT_EVAL   # per launch (one step, this rank)
-    achieved = algo_bytes / (kern_ms * 1e-3) / 1e9 if kern_ms > 0 else float("nan")
+    achieved = None if kern_ms is None else algo_bytes / (kern_ms * 1e-3) / 1e9 if kern_ms > 0 else float("nan")
 
     out = None
     if rank == 0:
@@ -296,7 +316,7 @@ def main():
             # clock settle (--settle-ms of wall time) and the `warmup` steps
             "untimed_launches_total": cold_launches + settle_launches + args.warmup,
             "ms_per_step": 1e3 * elapsed / max(args.steps, 1),
-            "value_one_batch_at_a_time": B * world / (serial_ms * 1e-3) if world == 1 else None,
+            "value_one_batch_at_a_time": B * world / (serial_ms * 1e-3) if world == 1 and serial_ms else None,   # (two in flight: with --full)
             "higher_is_better": True,
             "scaling": "weak",
             "vs_baseline": None,
@@ -331,7 +351,7 @@ def main():
                     "depth": depth,
                     "note": "value / ms_per_step: `steps` launches of one context issued back to back with ndtpso_set_pipeline_depth(%d); "
                             "one_batch_at_a_time: the same launches one after the other on one stream (what rounds 1-2 reported)" % depth,
-                    "one_batch_at_a_time": {"alignments_per_s": B * world / (serial_ms * 1e-3) if world == 1 else None,
+                    "one_batch_at_a_time": {"alignments_per_s": B * world / (serial_ms * 1e-3) if world == 1 and serial_ms else None,
                                             "ms_per_step": serial_ms, "kernel_ms_by_events": kern_ms},
                     "poses_equal_between_the_two_output_sets": poses_equal_between_sets,
                 },
@@ -350,8 +370,10 @@ def main():
         allp = sharding.gather_poses(mine, equal_sizes=True, force=True)
         own = torch.tensor([1 if torch.equal(allp[rank * B:(rank + 1) * B], mine) and allp.shape[0] == world * B else 0], device=dev)
         dist.all_reduce(own, op=dist.ReduceOp.MIN)
+        if args.dump_outputs and rank == 0:   # the poses as the step's gather delivers them (all ranks'); cost and status of rank 0's pairs
+            _dump_outputs(args.dump_outputs, capi, allp.cpu().numpy(), last_cost, last_stats)
         g_us = []
-        for _ in range(25):
+        for _ in range(25 if args.full else 0):   # (the duration of the collective: a measurement of its own)
             a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
             a.record(stream)
             sharding.gather_poses(mine, equal_sizes=True, force=True)
@@ -364,7 +386,7 @@ def main():
             except Exception:  # noqa: BLE001
                 ver = None
             out["rccl"] = {"ranks_seen": ranks_seen, "world_size": dist.get_world_size(), "backend": dist.get_backend(),
-                           "version": ver, "gather_us_median": float(np.median(g_us[5:])),
+                           "version": ver, "gather_us_median": float(np.median(g_us[5:])) if g_us else None,
                            "gather_bytes_per_rank": int(B * 24), "every_rank_found_its_poses_in_the_gather": bool(int(own.item())),
                            "launch": "one process per GPU (torch.distributed), %s" % ("started by bench.py itself" if os.environ.get("NDTPSO_BENCH_SELF_LAUNCHED") == "1" else "started by a launcher")}
             assert ranks_seen == world == args.gpus, (ranks_seen, world, args.gpus)
@@ -375,7 +397,7 @@ def main():
     # The extras (single-pair latency, the other score modes, config 5, the live sequences): rank 0 of a ONE-GPU run only.  With
     # N > 1 the other ranks would sit in the closing barrier for as long as rank 0 takes over them -- minutes of a collective in
     # flight on N - 1 devices for figures the N = 1 line of the same driver pass already carries.
-    extras = rank == 0 and world == 1 and not args.no_latency
+    extras = args.full and rank == 0 and world == 1 and not args.no_latency
     # single-pair latency (BASELINE config 2)
     if extras:
         torch.cuda.synchronize()
@@ -476,7 +498,7 @@ def main():
             out["extra"]["live_replicas"] = {"error": str(e)}
 
     # CPU baseline: the oracle -- a port of the reference's algorithm -- on this box's host cores
-    if rank == 0 and world == 1 and args.cpu_sample > 0:
+    if args.full and rank == 0 and world == 1 and args.cpu_sample > 0:
         out["cpu_baseline"] = _cpu_baseline(pairs, min(args.cpu_sample, B), P, I)
         opose = out["cpu_baseline"].pop("_poses")
         out["extra"]["parity_max_abs_dpose_vs_oracle"] = np.abs(pose[:len(opose)] - opose).max(axis=0).tolist()
@@ -488,6 +510,18 @@ def main():
         dist.barrier()
         dist.destroy_process_group()
     _print_result(out if rank == 0 else None, stdout_fd)
+
+
+def _dump_outputs(path, capi, pose, cost, stats):
+    """--dump-outputs: what a caller of the timed path holds after its last step, as float64 `.npy` files -- pose (pairs x 3),
+    cost (pairs), status (pairs: the flags of AlignStats, 0 = fine) and n_points (pairs: the scan points that were scored).
+    The inputs are a function of the arguments alone (synth.make_pairs, fixed seed), so two builds run with the same arguments
+    can be held against each other file by file.  The other words of AlignStats are left out: device timestamps and counters
+    of how the work was scheduled, which describe a run, not its result.  (A few KB: far below any limit worth sampling for.)"""
+    os.makedirs(path, exist_ok=True)
+    st = np.ascontiguousarray(stats).view(capi.STATS_DTYPE).reshape(-1)
+    for name, a in (("pose", pose), ("cost", cost), ("status", st["status"]), ("n_points", st["n_points"])):
+        np.save(os.path.join(path, name + ".npy"), np.ascontiguousarray(a, dtype=np.float64))
 
 
 def _print_result(out, stdout_fd):
@@ -511,7 +545,7 @@ def _free_port() -> int:
 
 
 def relaunch_command(argv, n_gpus, port=None):
-    """What `bench.py --gpus N` (N > 1) started WITHOUT a launcher executes in its own place: the launcher line of the
+    """What `bench.py --gpus N` (N > 1) started WITHOUT a launcher starts as a child process: the launcher line of the
     task's contract, one rank per GPU over RCCL, rendezvous on 127.0.0.1."""
     return [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(int(n_gpus)),
             "--master-addr", "127.0.0.1", "--master-port", str(int(port) if port else _free_port()),
@@ -519,10 +553,10 @@ def relaunch_command(argv, n_gpus, port=None):
 
 
 def launch_plan(gpus, sharded, environ, n_devices, argv):
-    """-> (kind, detail).  kind: 'run' (this process is a rank -- or the only one), 'relaunch' (detail = the command to exec),
+    """-> (kind, detail).  kind: 'run' (this process is a rank -- or the only one), 'relaunch' (detail = the command to start),
     'sharded' (the one process of --sharded-capi), 'fail' (detail = the reason; the caller exits with code 2).
     Rules: --gpus N must be what runs.  WORLD_SIZE set (a launcher started us): it must equal N, and LOCAL_RANK must name a
-    visible device.  WORLD_SIZE unset and N > 1: N devices must be visible and this process re-executes itself under
+    visible device.  WORLD_SIZE unset and N > 1: N devices must be visible and this process starts itself again, as a child, under
     python -m torch.distributed.run.  --sharded-capi: one process, N devices visible -- unless NDTPSO_SHARD_VIRTUAL=N (the
     shard group's test mode: N shards on the visible devices, gather staged through the host; flagged in the result)."""
     if gpus < 1:
@@ -542,8 +576,8 @@ def launch_plan(gpus, sharded, environ, n_devices, argv):
             return "fail", "--gpus %d but %d HIP device(s) visible" % (gpus, n_devices)
         if gpus == 1 and environ.get("NDTPSO_BENCH_FORCE_DIST") != "1":
             return "run", None
-        # (NDTPSO_BENCH_FORCE_DIST=1 with --gpus 1: the same re-execution with one rank -- a one-GPU box runs the very path, exec
-        # included, that `--gpus 8` takes)
+        # (NDTPSO_BENCH_FORCE_DIST=1 with --gpus 1: the same relaunch with one rank -- a one-GPU box runs the very path, child
+        # process included, that `--gpus 8` takes)
         return "relaunch", relaunch_command(argv, gpus)
     if int(ws) != gpus:
         return "fail", "started with WORLD_SIZE=%s but --gpus %d: refusing to report a number for another number of GPUs" % (ws, gpus)
@@ -606,7 +640,9 @@ def _main_sharded(args, torch):
         per_call.append(grp.last_timing()[1].copy())
     elapsed = time.perf_counter() - t0     # (every call returns with all the devices synchronised)
     ranks_seen = grp.verify_gather()
-    pose, cost, stats = step(fetch=True)
+    pose, cost, stats = step(fetch=True)   # (the timed steps leave their results on the devices: one more, identical, step fetches them)
+    if args.dump_outputs:
+        _dump_outputs(args.dump_outputs, capi, pose, cost, stats)
     per, _ = grp.last_timing()
     assert (stats["status"] == 0).all(), "alignments flagged: %d" % int((stats["status"] != 0).sum())
     assert ranks_seen == G, "the gather moved %d of %d shards' poses" % (ranks_seen, G)
@@ -797,11 +833,11 @@ def _roofline(stats, evals_nominal, kern_ms, algo_bytes, hbm_equiv_gbs, step_ms,
     # flight a step is shorter than a launch, because the next batch fills the compute units the slowest alignments of
     # this one leave idle); the per-launch figures (one launch at a time, what a kernel trace averages) carry their name.
     achieved = flops / (step_ms * 1e-3) / 1e12
-    achieved_launch = flops / (kern_ms * 1e-3) / 1e12
+    achieved_launch = flops / (kern_ms * 1e-3) / 1e12 if kern_ms is not None else None   # (None: not measured, see --full)
     peak = flops / t_peak_s / 1e12
     r = {"bound": "valu", "achieved": achieved, "peak": peak, "unit": "TFLOP/s", "frac": achieved / peak,
          "regime": "%d batch(es) in flight: flops of one step / ms_per_step (%.3f ms), the regime of `value`" % (depth, step_ms),
-         "achieved_per_launch": achieved_launch, "frac_per_launch": achieved_launch / peak,
+         "achieved_per_launch": achieved_launch, "frac_per_launch": achieved_launch / peak if kern_ms is not None else None,
          "traffic": _pmc_traffic_bytes(f64), "kernel": "k_align_pairs (fused scan ingest + cell statistics + PSO)",
          "kernel_ms": kern_ms, "algorithmic_point_evals_per_launch": point_evals,
          "flops_per_point_eval": {"fp64": FLOP_FP64, "fp32": FLOP_FP32, "exp": FLOP_EXP},
@@ -817,11 +853,12 @@ def _roofline(stats, evals_nominal, kern_ms, algo_bytes, hbm_equiv_gbs, step_ms,
         issue_peak = N_SIMD * 64.0 / (ns_chunk * 1e-9)
         r["floor"] = {"valu_instructions_per_64_points": mix["valu_per_chunk"], "valu_issue_ns_per_64_points": ns_chunk,
                       "floor_ms_per_launch": point_evals / issue_peak * 1e3,
-                      "frac_of_kernel_ms": point_evals / issue_peak * 1e3 / kern_ms,
+                      "frac_of_kernel_ms": point_evals / issue_peak * 1e3 / kern_ms if kern_ms is not None else None,
                       "what": "issue time of the score loop's own instruction mix on 1024 SIMDs (a shorter loop lowers it): a tuning "
                               "figure, not the roofline",
                       "source": "profiles/%s (scripts/isa_mix.py: llvm-objdump of the shipped kernel x scripts/ubench_valu.hip on this chip)" % mix_name}
-    r["hbm_effective"] = {"achieved": hbm_equiv_gbs, "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": hbm_equiv_gbs / HBM_PEAK_GBS,
+    r["hbm_effective"] = {"achieved": hbm_equiv_gbs, "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                          "frac": hbm_equiv_gbs / HBM_PEAK_GBS if hbm_equiv_gbs is not None else None,
                           "algorithmic_bytes_per_launch": algo_bytes,
                           "note": "SURVEY 8(d)'s streaming-equivalent accounting: 40 B per point evaluation (16 B point + 24 B cell "
                                   "record); the kernel serves them from LDS, so this exceeds the HBM peak by construction -- HBM is "

@@ -15,7 +15,7 @@ for r in range(args.rounds):
     for lib in args.libs:
         for score in args.score.split(","):
             env = dict(os.environ, NDTPSO_LIB=os.path.abspath(lib))
-            out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", str(args.steps), "--warmup", "10", "--cpu-sample", "0",
+            out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", str(args.steps), "--warmup", "10", "--full", "--cpu-sample", "0",
                                   "--no-latency", "--score", score], env=env, capture_output=True, text=True)
             try:
                 d = json.loads(out.stdout.strip().splitlines()[-1])

@@ -12,10 +12,10 @@ python scripts/isa_mix.py --kernel "k_align_pairs<0, 3, false, true, true, 0, fa
 python scripts/isa_mix.py --kernel "k_align_pairs<1, 9, false, false, false, 2, false>" --marker v_rndne_f64 --marker-span 90 --ubench $OUT/ubench_valu.txt --out $OUT/isa_mix_f64.json --dump $OUT/score_loop_isa_f64.txt > /dev/null
 cp $OUT/isa_mix.json profiles/r06_isa_mix.json   # the bench line's roofline.floor reads them
 cp $OUT/isa_mix_f64.json profiles/r06_isa_mix_f64.json
-timeout 600 python bench.py > $OUT/bench.json 2> $OUT/bench.err
-timeout 300 python bench.py --pipeline 1 --no-latency --cpu-sample 0 > $OUT/bench_one_at_a_time.json 2>> $OUT/bench.err
+timeout 600 python bench.py --full > $OUT/bench.json 2> $OUT/bench.err
+timeout 300 python bench.py --full --pipeline 1 --no-latency --cpu-sample 0 > $OUT/bench_one_at_a_time.json 2>> $OUT/bench.err
 # the other two score modes of the same workload (fp64 score throughout; plain fp32 score), two batches in flight and one at a time
-for sc in f64 f32; do timeout 300 python bench.py --score $sc --no-latency --cpu-sample 0 > $OUT/bench_$sc.json 2>> $OUT/bench.err; done
+for sc in f64 f32; do timeout 300 python bench.py --full --score $sc --no-latency --cpu-sample 0 > $OUT/bench_$sc.json 2>> $OUT/bench.err; done
 # kernel traces (own runs): one batch at a time -- the per-launch duration the roofline divides by -- and two in flight
 (cd /tmp && export TMPDIR=/tmp && rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace1 -o t -- python $GRAFT_REPO_ROOT/bench.py --pipeline 1 --steps 40 --warmup 20 --cpu-sample 0 --no-latency > $OUT/trace1.log 2>&1)
 (cd /tmp && export TMPDIR=/tmp && rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace2 -o t -- python $GRAFT_REPO_ROOT/bench.py --pipeline 2 --steps 40 --warmup 20 --cpu-sample 0 --no-latency > $OUT/trace2.log 2>&1)
@@ -29,7 +29,7 @@ timeout 300 python scripts/phase_budget.py --config config3 --score exact --out 
 timeout 300 python scripts/phase_budget.py --config beams361 --score exact --out $OUT/phase_budget_361.json >> $OUT/budget.log 2>&1
 # the two launch conventions of N GPUs as far as one GPU goes: bench.py starting its own rank (RCCL path), the one-process sharded
 # entry on the one device through real RCCL, and eight VIRTUAL shards on the one device (plumbing only, flagged in the line)
-NDTPSO_BENCH_FORCE_DIST=1 timeout 300 python bench.py --gpus 1 --no-latency --cpu-sample 0 > $OUT/bench_self_launched_rccl.json 2>> $OUT/bench.err
+NDTPSO_BENCH_FORCE_DIST=1 timeout 300 python bench.py --full --gpus 1 --no-latency --cpu-sample 0 > $OUT/bench_self_launched_rccl.json 2>> $OUT/bench.err
 timeout 300 python bench.py --sharded-capi --gpus 1 > $OUT/bench_sharded_capi_g1.json 2>> $OUT/bench.err
 NDTPSO_SHARD_VIRTUAL=8 timeout 300 python bench.py --sharded-capi --gpus 8 --steps 40 > $OUT/bench_sharded_capi_virtual8.json 2>> $OUT/bench.err
 # replicas of the live sequence in one process, defaults and the round-5 behaviour (spinning waiters, clusters whatever is in flight)

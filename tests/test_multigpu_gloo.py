@@ -152,8 +152,8 @@ def test_bench_multi_rank_path_under_torch_distributed_run(tmp_path):
     env = dict(os.environ, NDTPSO_BENCH_FORCE_DIST="1", HSA_ENABLE_IPC_MODE_LEGACY="0")
     r = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1",
                         "--master-addr", "127.0.0.1", "--master-port", "29547", os.path.join(ROOT, "bench.py"),
-                        "--gpus", "1", "--steps", "10", "--warmup", "3", "--cpu-sample", "0", "--no-latency"],
-                       env=env, capture_output=True, text=True, timeout=900)
+                        "--gpus", "1", "--steps", "10", "--warmup", "3", "--full", "--cpu-sample", "0", "--no-latency"],
+                       env=env, capture_output=True, text=True, timeout=900)   # (--full: the gather's duration is asserted below)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
     assert len(lines) == 1, r.stdout
@@ -167,8 +167,8 @@ def test_bench_multi_rank_path_under_torch_distributed_run(tmp_path):
 @pytest.mark.gpu
 def test_bench_starts_its_own_ranks_when_no_launcher_did():
     """`python bench.py --gpus N` WITHOUT torch.distributed.run around it (how the driver starts the N = 1 line): for N > 1 it
-    re-executes itself under the launcher.  On the one-GPU box NDTPSO_BENCH_FORCE_DIST=1 sends --gpus 1 down the same road --
-    the exec, the rendezvous on 127.0.0.1, a process group of one rank over RCCL, the all_gather every step."""
+    starts itself again under the launcher, as a child process.  On the one-GPU box NDTPSO_BENCH_FORCE_DIST=1 sends --gpus 1 down
+    the same road -- the child process, the rendezvous on 127.0.0.1, a process group of one rank over RCCL, the all_gather every step."""
     import json
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     env.update(NDTPSO_BENCH_FORCE_DIST="1", HSA_ENABLE_IPC_MODE_LEGACY="0")
