@@ -9,6 +9,7 @@
 #ifndef NDTPSO_SLAM_AMD_NDTFRAME_H
 #define NDTPSO_SLAM_AMD_NDTFRAME_H
 
+#include <cstddef>
 #include <cstdint>
 #include <utility>
 #include <vector>
@@ -29,6 +30,16 @@ struct ndtpso_map;     // device-resident map
 namespace ndtpso_host {
 struct Ctx;
 }
+
+class NDTFrame;
+// One request of NDTFrame::alignBatch (not in the reference): pose = ref->align(guess, cur), ok = ref->lastAlignOk() after it.
+struct NDTAlignRequest {
+  NDTFrame* ref;
+  const NDTFrame* cur;
+  Vector3d guess;
+  Vector3d pose;  // out
+  bool ok;        // out
+};
 
 class NDTFrame {
  public:
@@ -77,6 +88,15 @@ class NDTFrame {
   // f.loadLaser(...); update(pose, &f); } -- same points, same order, same bits.
   void addScan(const Vector3d& pose, const vector<float>& laser_data, const float& min_angle, const float& angle_increment,
                const float& max_range);
+  // Several align() calls at once: observably identical to reqs[i].pose = reqs[i].ref->align(reqs[i].guess, reqs[i].cur) for
+  // i = 0 .. n - 1 in that order -- the same deviation rule per frame, the same PSOConfig, the std::rand() stream drawn in request
+  // order, `built` / lastAlignOk() / the refusal of update() after a failure as those calls would leave them, a failed request
+  // returning its guess -- but consecutive requests on DIFFERENT resident reference frames of the calling thread's device context,
+  // with device-resident scans, share one launch (ndtpso_map_align_batch, include/ndtpso_hip.h): R robots served by one host
+  // thread.  A reference frame that appears a second time closes the current launch (its deviation depends on the first
+  // result), and so does a frame that one request aligns against and another aligns as scan; any other request takes align() itself, in its place.  The reference aligns one scan at a time
+  // (ndtpso_slam_node.cpp:182-194).
+  static void alignBatch(NDTAlignRequest* reqs, size_t n);
   // new-frame points in the order cost_function visits them (cells, then insertion; core.cpp:33-36)
   void collectPoints(std::vector<double>& xy) const;
   const NDTPSOConfig& config() const { return s_config; }

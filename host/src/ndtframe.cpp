@@ -33,8 +33,9 @@ uint64_t map_pool_bytes(unsigned num_cells) {
   // 512 B per 32 points of one window slot.  A one-cell frame that is only ever updated (the node's global_map_,
   // ndtpso_slam_node.cpp:70-72,200-203) is never built, so it never rotates and keeps every point it was given.
   const char* e = std::getenv(num_cells == 1 ? "NDTPSO_GLOBAL_MAP_POOL_MB" : "NDTPSO_MAP_POOL_MB");
-  const uint64_t mb = e ? (uint64_t)std::strtoull(e, nullptr, 10) : (num_cells == 1 ? 4096u : 1024u);
-  return (mb ? mb : 1u) << 20;
+  // (a fraction is taken as one: "0.03125" is a pool of 64 chunks, which the tests of the exhaustion path fill with one scan)
+  const double mb = e ? std::strtod(e, nullptr) : (num_cells == 1 ? 4096. : 1024.);
+  return (uint64_t)((mb > 0. ? mb : 1.) * 1048576.);
 }
 }  // namespace
 
@@ -577,20 +578,117 @@ double NDTFrame::cost(const Vector3d& trans, const NDTFrame* new_frame) {
 // reference: align, ndtframe.cpp:251-266.  The reference passes no config to pso_optimization (:257), so the
 // frame's own PSOConfig is never used and every alignment runs the default 30 x 50.  That is what happens here
 // too; NDTPSO_ALIGN_FRAME_CONFIG=1 in the environment makes align() honour the frame's PSOConfig instead.
-Vector3d NDTFrame::align(Vector3d initial_guess, const NDTFrame* const new_frame) {
-  Vector3d deviation = s_iter < 2 ? Vector3d(.1, .1, 3.1415E-3) : Vector3d((s_pose_diff * 2.).array().abs());
-  ++s_iter;
+namespace {
+bool align_uses_frame_config() {
   static const bool frame_config = [] {
     const char* e = std::getenv("NDTPSO_ALIGN_FRAME_CONFIG");
     return e && e[0] == '1';
   }();
-  Vector3d pose = optimize(initial_guess, new_frame, deviation, frame_config ? s_config.psoConfig : PSOConfig());
+  return frame_config;
+}
+}  // namespace
+
+Vector3d NDTFrame::align(Vector3d initial_guess, const NDTFrame* const new_frame) {
+  Vector3d deviation = s_iter < 2 ? Vector3d(.1, .1, 3.1415E-3) : Vector3d((s_pose_diff * 2.).array().abs());
+  ++s_iter;
+  Vector3d pose = optimize(initial_guess, new_frame, deviation, align_uses_frame_config() ? s_config.psoConfig : PSOConfig());
 #if TRANSFORM_POSE_AFTER_ALIGN
   pose -= s_trans;
 #endif
   s_pose_diff = pose - s_prev_pose;
   s_prev_pose = pose;
   return pose;
+}
+
+// Several align() calls, the device work of independent ones in one launch (see ndtframe.h).  Everything a sequence of align()
+// calls does on the host is done here in the same order: deviation and ++s_iter per frame (align), the map and the rand() draws
+// per request (optimize), then ONE ndtpso_map_align_batch for the run, then `built`, lastAlignOk(), the thread's failure flag
+// and s_pose_diff / s_prev_pose per request, again in order.
+void NDTFrame::alignBatch(NDTAlignRequest* reqs, size_t n) {
+  if (!reqs) return;
+  ndtpso_host::Ctx* const mine = ndtpso_host::thread_ctx();
+  auto batchable = [&](const NDTAlignRequest& r) {
+    if (!r.ref || !r.cur || align_uses_frame_config()) return false;  // (frames' own PSOConfigs: one cfg per launch)
+    const NDTFrame* c = r.cur;
+    return r.ref->s_resident && r.ref->dev() == mine && c->dev() == mine && c->s_resident && c->d_scan_ && !c->d_map_;
+  };
+  size_t i = 0;
+  while (i < n) {
+    size_t j = i;
+    while (j < n && batchable(reqs[j])) {
+      // The run ends before a request whose reference frame it has already seen (its deviation depends on the first result),
+      // and before one that uses as reference a frame an earlier request aligns as scan, or the other way round: making the
+      // reference's device map (ensureMap) turns such a frame's point list into a map, which sequential calls do between the two
+      // alignments, not before both.
+      bool again = false;
+      for (size_t k = i; k < j && !again; ++k)
+        again = reqs[k].ref == reqs[j].ref || reqs[k].cur == reqs[j].ref || reqs[k].ref == reqs[j].cur;
+      if (again) break;
+      ++j;
+    }
+    if (j - i < 2) {  // align() itself, in its place
+      NDTAlignRequest& r = reqs[i];
+      r.pose = r.ref->align(r.guess, r.cur);
+      r.ok = r.ref->lastAlignOk();
+      ++i;
+      continue;
+    }
+    ndtpso_host::Use use(mine);
+    const size_t cnt = j - i;
+    const ndtpso_pso_config abi = to_abi(PSOConfig());  // (what align() passes on, ndtframe.cpp:257)
+    const size_t n_draw = ndtpso_rand_draws(&abi);
+    std::vector<ndtpso_map_align_job> jobs(cnt);
+    std::vector<int32_t> draws(cnt * n_draw);
+    std::memset(jobs.data(), 0, cnt * sizeof(ndtpso_map_align_job));
+    bool no_map = false;
+    for (size_t k = 0; k < cnt; ++k) {
+      NDTAlignRequest& r = reqs[i + k];
+      NDTFrame* f = r.ref;
+      const Vector3d deviation = f->s_iter < 2 ? Vector3d(.1, .1, 3.1415E-3) : Vector3d((f->s_pose_diff * 2.).array().abs());
+      ++f->s_iter;
+      ndtpso_map_align_job& job = jobs[k];
+      job.map = f->ensureMap();
+      no_map = no_map || !job.map;
+      job.new_points = r.cur->d_scan_;
+      ndtpso_host::draw_rand(&draws[k * n_draw], n_draw);  // drawn even if the device call fails (optimize)
+      job.rand_table = &draws[k * n_draw];
+      job.guess[0] = job.pose[0] = r.guess.x();
+      job.guess[1] = job.pose[1] = r.guess.y();
+      job.guess[2] = job.pose[2] = r.guess.z();
+      job.deviation[0] = deviation.x();
+      job.deviation[1] = deviation.y();
+      job.deviation[2] = deviation.z();
+    }
+    int rc_call = NDTPSO_OK;
+    if (no_map) {  // (a frame whose device map could not be made fails alone, as its align() would: one call each)
+      for (size_t k = 0; k < cnt; ++k)
+        jobs[k].rc = ndtpso_map_align(jobs[k].map, jobs[k].new_points, jobs[k].guess, jobs[k].deviation, &abi, 0u, jobs[k].rand_table,
+                                      ndtpso_host::score_mode(), jobs[k].pose, nullptr, nullptr);
+    } else {
+      rc_call = ndtpso_map_align_batch(ndtpso_host::device(), jobs.data(), (uint32_t)cnt, &abi, ndtpso_host::score_mode());
+    }
+    bool some_job_failed = false;
+    for (size_t k = 0; k < cnt; ++k) some_job_failed = some_job_failed || jobs[k].rc != NDTPSO_OK;
+    for (size_t k = 0; k < cnt; ++k) {
+      NDTAlignRequest& r = reqs[i + k];
+      NDTFrame* f = r.ref;
+      // (a call refused as a whole -- no device context, a HIP error before the launch -- failed every request)
+      const int rc = (rc_call != NDTPSO_OK && !some_job_failed) ? rc_call : jobs[k].rc;
+      const bool ok = ndtpso_host::check(rc, "align");
+      if (ok) f->built = true;
+      f->s_last_align_ok = ok;
+      t_last_align_failed = !ok;
+      Vector3d pose = ok ? Vector3d(jobs[k].pose[0], jobs[k].pose[1], jobs[k].pose[2]) : r.guess;
+#if TRANSFORM_POSE_AFTER_ALIGN
+      pose -= f->s_trans;
+#endif
+      f->s_pose_diff = pose - f->s_prev_pose;
+      f->s_prev_pose = pose;
+      r.pose = pose;
+      r.ok = ok;
+    }
+    i = j;
+  }
 }
 
 // ---- bookkeeping / export members outside the accelerated path ---------------------------------------------

@@ -287,6 +287,39 @@ int ndtpso_map_speculate_build(ndtpso_map *map);
 int ndtpso_map_align(ndtpso_map *map, const ndtpso_points *new_points, const double guess[3], const double deviation[3],
                      const ndtpso_pso_config *cfg, uint32_t seed, const int32_t *rand_table, int score_mode,
                      double out_pose[3], double *out_cost, ndtpso_align_stats *stats);
+/* Several ndtpso_map_align calls of one context in ONE launch: the robots a process serves, or several start poses for one
+ * scan.  The reference has no counterpart -- its node aligns one scan at a time (ndtpso_slam_node.cpp:182) -- so the contract is
+ * the single call's: job j's pose, cost and stats (status, n_points, n_built, gbest_updates) are bit for bit what
+ * ndtpso_map_align(jobs[j].map, ...) returns for the same arguments when called alone, in every score mode, and afterwards every
+ * map is in the state the same calls made in job order would leave it (lazy build done, a pending speculative build committed,
+ * header known to the host).  Jobs may name different maps -- grids, windows and table sizes may all differ -- or the same map
+ * several times.  Each distinct map is prepared once; the jobs whose plan has a job kernel (fp32 score on the dense table,
+ * plain or arbitrating, and the fp64 score on the bitmap of power-of-two cells, swarm in LDS) run as one workgroup or one
+ * cluster of workgroups each in a common launch and report through one pinned result slot each; every other job, a call of one
+ * job, and a job that comes back flagged (fp32 score in its underflow regime, a late-bound window outgrown, a cluster that did
+ * not meet) runs alone through ndtpso_map_align's own path (route 0).
+ * Returns NDTPSO_E_ARG before anything is enqueued for a null pointer, n_jobs == 0, a map or scan of another context or a bad
+ * score mode; else NDTPSO_OK if every job's rc is 0, else the first failing job's rc (the other jobs are completed). */
+typedef struct {
+  ndtpso_map *map;                 /* in: reference frame (may repeat across jobs) */
+  const ndtpso_points *new_points; /* in: loaded scan */
+  double guess[3], deviation[3];   /* in */
+  uint32_t seed, flags;            /* in: flags bit 0 = cost wanted */
+  const int32_t *rand_table;       /* in: ndtpso_rand_draws(cfg) values, or NULL = device replay of srand(seed) */
+  double pose[3], cost;            /* out */
+  ndtpso_align_stats stats;        /* out */
+  int32_t rc;                      /* out: NDTPSO_OK or this job's error */
+  int32_t route;                   /* out: 1 = batch kernel on one workgroup, K >= 2 = batch kernel on a cluster of K,
+                                      0 = the single-alignment path (ndtpso_map_align's) */
+} ndtpso_map_align_job;
+#define NDTPSO_MAP_ALIGN_JOB_BYTES 152
+#if defined(__cplusplus)
+static_assert(sizeof(ndtpso_map_align_job) == NDTPSO_MAP_ALIGN_JOB_BYTES, "ndtpso_map_align_job layout");
+#elif defined(__STDC_VERSION__) && __STDC_VERSION__ >= 201112L
+_Static_assert(sizeof(ndtpso_map_align_job) == NDTPSO_MAP_ALIGN_JOB_BYTES, "ndtpso_map_align_job layout");
+#endif
+int ndtpso_map_align_batch(ndtpso_ctx *ctx, ndtpso_map_align_job *jobs, uint32_t n_jobs,
+                           const ndtpso_pso_config *cfg, int score_mode);
 /* cost_function (core.cpp:26-48) of a loaded scan against the map at n_poses candidate poses (3 doubles each) */
 int ndtpso_map_cost(ndtpso_map *map, ndtpso_points *new_points, const double *poses, uint32_t n_poses, int score_mode,
                     double *costs);
@@ -437,6 +470,14 @@ int ndtpso_device_math(ndtpso_ctx *ctx, int kind, const double *x, uint32_t n, d
  * skips the check. */
 int ndtpso_exact_check(ndtpso_ctx *ctx, int *state, uint32_t *arbitrated_batch, uint32_t *arbitrated_single, double *ms);
 int ndtpso_exact_check_report(ndtpso_ctx *ctx, char *buf, uint32_t cap);
+/* The same rule for the two arbitrating kernels of ndtpso_map_align_batch (jobs of one launch on one workgroup each, on a cluster
+ * of workgroups each): the first exact-mode call of that entry on a device sends the same fixed problem through both, as jobs of
+ * one launch against a resident map, and compares with the fp64 mode bit for bit.  A family that fails refuses the exact mode to
+ * that entry only (its exact-mode jobs run NDTPSO_SCORE_F64; ndtpso_last_error explains).  ndtpso_exact_check_jobs runs it if it
+ * has not run: state 1 passed, 2 refused, 0 no verdict.  ndtpso_exact_check_report lists the two under the key "job_families"
+ * (same fields as "families"; empty until the check has run).  The reference has nothing of the kind: it has one score, in fp64
+ * (ndtcell.cpp:70-77). */
+int ndtpso_exact_check_jobs(ndtpso_ctx *ctx, int *state);
 
 #ifdef __cplusplus
 }

@@ -12,8 +12,13 @@ import subprocess
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 SRC = os.path.join(HERE, "csrc", "ndtpso_hip.hip")
-DEPS = [SRC, os.path.join(HERE, "csrc", "ndtpso_kernels.hpp"), os.path.join(HERE, "csrc", "ndtpso_map.inc"),
+# the job kernels of ndtpso_map_align_batch: a translation unit of their own (see the file's header), same flags, same library
+SRC_JOBS = os.path.join(HERE, "csrc", "ndtpso_align_jobs.hip")
+SRCS = [SRC, SRC_JOBS]
+DEPS = [SRC, SRC_JOBS, os.path.join(HERE, "csrc", "ndtpso_kernels.hpp"), os.path.join(HERE, "csrc", "ndtpso_map.inc"),
         os.path.join(HERE, "csrc", "ndtpso_pairs_body.inc"),
+        os.path.join(HERE, "csrc", "ndtpso_align_body.inc"), os.path.join(HERE, "csrc", "ndtpso_map_batch.inc"),
+        os.path.join(HERE, "csrc", "ndtpso_device_common.inc"), os.path.join(HERE, "csrc", "ndtpso_align_jobs.h"),
         os.path.join(HERE, "csrc", "ndtpso_shard.inc"), os.path.join(HERE, "csrc", "ndtpso_selftest.inc"),
         os.path.join(os.path.dirname(HERE), "include", "ndtpso_hip.h")]
 LIB_DIR = os.path.join(HERE, "lib")
@@ -72,7 +77,7 @@ def build_hip(force: bool = False, verbose: bool = False) -> str:
             try:
                 if force or needs_build():  # somebody else may have built it while this process waited
                     tmp = "%s.%d.tmp" % (LIB, os.getpid())
-                    cmd = [hipcc()] + FLAGS + [SRC, "-o", tmp]
+                    cmd = [hipcc()] + FLAGS + SRCS + ["-o", tmp]
                     if verbose:
                         print(" ".join(cmd[:-1] + [LIB]))
                     try:
@@ -117,7 +122,7 @@ def build_variant(name: str, force: bool = False, verbose: bool = False) -> str:
     if not fresh:
         os.makedirs(LIB_DIR, exist_ok=True)
         tmp = "%s.%d.tmp" % (out, os.getpid())
-        cmd = [hipcc()] + FLAGS + VARIANTS[name] + [SRC, "-o", tmp]
+        cmd = [hipcc()] + FLAGS + VARIANTS[name] + SRCS + ["-o", tmp]
         if verbose:
             print(" ".join(cmd[:-1] + [out]))
         try:

@@ -96,6 +96,13 @@ class MapInfo(C.Structure):
                 ("pool_bump", C.c_int32), ("pool_free", C.c_int32), ("n_points", C.c_uint64)]
 
 
+class MapAlignJob(C.Structure):
+    """ndtpso_map_align_job (include/ndtpso_hip.h): one alignment of ndtpso_map_align_batch"""
+    _fields_ = [("map", C.c_void_p), ("new_points", C.c_void_p), ("guess", C.c_double * 3), ("deviation", C.c_double * 3),
+                ("seed", C.c_uint32), ("flags", C.c_uint32), ("rand_table", C.POINTER(C.c_int32)),
+                ("pose", C.c_double * 3), ("cost", C.c_double), ("stats", AlignStats), ("rc", C.c_int32), ("route", C.c_int32)]
+
+
 STATS_DTYPE = np.dtype([("n_points", "<u4"), ("n_built", "<u4"), ("cost_evals", "<u4"), ("rounds", "<u4"),
                         ("gbest_updates", "<u4"), ("status", "<u2"), ("arbitrated", "<u2"), ("t_start", "<u4"),
                         ("t_end", "<u4")])   # the C struct's `status` word: flags in its low half, SCORE_EXACT's count above
@@ -111,12 +118,13 @@ EXPORTS = [
     "ndtpso_points_create", "ndtpso_points_destroy", "ndtpso_points_load_scan", "ndtpso_points_set", "ndtpso_points_get",
     "ndtpso_map_create", "ndtpso_map_destroy", "ndtpso_map_reset", "ndtpso_map_clear", "ndtpso_map_mark_unbuilt", "ndtpso_map_insert", "ndtpso_map_insert_host",
     "ndtpso_map_build", "ndtpso_map_speculate_build", "ndtpso_map_align", "ndtpso_map_cost", "ndtpso_map_get_info", "ndtpso_map_get_cells", "ndtpso_map_get_points",
-    "ndtpso_map_get_occupancy",
+    "ndtpso_map_get_occupancy", "ndtpso_map_align_batch",
     "ndtpso_shard_group_create", "ndtpso_shard_group_destroy", "ndtpso_shard_group_size", "ndtpso_shard_last_error",
     "ndtpso_shard_range", "ndtpso_align_pairs_sharded", "ndtpso_align_pairs_sharded_dev", "ndtpso_shard_last_timing",
     "ndtpso_shard_gathered", "ndtpso_shard_group_describe", "ndtpso_shard_verify_gather",
     "ndtpso_shard_last_gather_device_us",
-    "ndtpso_selftest_exp", "ndtpso_device_math", "ndtpso_exact_check", "ndtpso_exact_check_report", "ndtpso_process_counters",
+    "ndtpso_selftest_exp", "ndtpso_device_math", "ndtpso_exact_check", "ndtpso_exact_check_report", "ndtpso_exact_check_jobs",
+    "ndtpso_process_counters",
 ]
 
 _lib = None
@@ -215,6 +223,8 @@ def load(build_if_missing: bool = True):
     L.ndtpso_map_speculate_build.argtypes = [vp]
     L.ndtpso_map_align.argtypes = [vp, vp, dp, dp, C.POINTER(PSOConfig), C.c_uint32, ip, C.c_int, dp, dp,
                                    C.POINTER(AlignStats)]
+    L.ndtpso_map_align_batch.argtypes = [vp, C.POINTER(MapAlignJob), C.c_uint32, C.POINTER(PSOConfig), C.c_int]
+    L.ndtpso_exact_check_jobs.argtypes = [vp, C.POINTER(C.c_int)]
     L.ndtpso_map_cost.argtypes = [vp, vp, dp, C.c_uint32, C.c_int, dp]
     L.ndtpso_map_get_info.argtypes = [vp, C.POINTER(MapInfo)]
     L.ndtpso_map_get_cells.argtypes = [vp, C.POINTER(CellRow), C.c_uint32, up]
@@ -332,6 +342,13 @@ class Context:
         if n < 0:
             self._chk(n)
         return json.loads(buf.value.decode())
+
+    def exact_check_jobs(self) -> int:
+        """The check of the exact mode's job kernels (ndtpso_map_align_batch), run now if it has not run: 1 passed, 2 refused,
+        0 no verdict.  exact_check_report()["job_families"] has its two families."""
+        st = C.c_int()
+        self._chk(self._lib.ndtpso_exact_check_jobs(self._h, C.byref(st)))
+        return st.value
 
     # ---- K3 ----
     def scan_to_points(self, ranges, geom: ScanGeom, trans=(0.0, 0.0, 0.0)) -> np.ndarray:
@@ -599,6 +616,40 @@ def align_pairs_describe(geom: ScanGeom, grid: Grid, cfg: PSOConfig, mode=SCORE_
     pl = PairsPlan()
     rc = L.ndtpso_align_pairs_describe(C.byref(geom), C.byref(grid), C.byref(cfg), mode, n_pairs, C.byref(pl))
     return rc, {k: getattr(pl, k) for k, _ in PairsPlan._fields_}
+
+
+def align_maps(ctx: "Context", jobs, cfg: PSOConfig, mode=SCORE_F32):
+    """ndtpso_map_align_batch: the alignments of `jobs` -- (ResidentMap, ResidentScan, guess, deviation, seed | rand_table) each,
+    a rand table being anything but an integer -- in one launch.  Returns poses [J, 3], costs [J], a dict of statistics arrays
+    (as align_pairs'), rc [J] and route [J] (1: the job kernel on one workgroup, K >= 2: on a cluster of K, 0: the single
+    path).  Raises only for the call's own errors (bad arguments); a job's failure is its rc."""
+    n = len(jobs)
+    arr = (MapAlignJob * max(n, 1))()
+    keep = []
+    n_draw = ctx._lib.ndtpso_rand_draws(C.byref(cfg))
+    for j, (m, scan, guess, deviation, seed) in zip(arr, jobs):
+        j.map, j.new_points = m._h, scan._h
+        j.guess[:] = [float(v) for v in _f64(guess, 3)]
+        j.deviation[:] = [float(v) for v in _f64(deviation, 3)]
+        j.flags = 1
+        if isinstance(seed, (int, np.integer)):
+            j.seed = int(seed)
+        else:
+            tab = np.ascontiguousarray(seed, dtype=np.int32)
+            assert tab.size >= n_draw
+            keep.append(tab)
+            j.rand_table = _p(tab, C.c_int32)
+    rc = ctx._lib.ndtpso_map_align_batch(ctx._h, arr, n, C.byref(cfg), int(mode))
+    rcs = np.array([j.rc for j in arr[:n]], dtype=np.int32)
+    if rc != OK and not (rcs != OK).any():
+        ctx._chk(rc)
+    poses = np.array([list(j.pose) for j in arr[:n]], dtype=np.float64).reshape(n, 3)
+    costs = np.array([j.cost for j in arr[:n]], dtype=np.float64)
+    st = np.zeros(n, dtype=STATS_DTYPE)
+    for i, j in enumerate(arr[:n]):
+        st[i] = np.frombuffer(bytes(j.stats), dtype=STATS_DTYPE)[0]
+    route = np.array([j.route for j in arr[:n]], dtype=np.int32)
+    return poses, costs, {k: st[k].copy() for k in STATS_DTYPE.names}, rcs, route
 
 
 class ResidentScan:

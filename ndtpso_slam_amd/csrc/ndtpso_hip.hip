@@ -21,236 +21,8 @@
 
 #include "../../include/ndtpso_hip.h"
 
-using namespace ndtpso;
-
-static_assert(sizeof(CellRow) == sizeof(ndtpso_cell_row), "cell row ABI");
-static_assert(sizeof(AlignStats) == sizeof(ndtpso_align_stats), "stats ABI");
-
-namespace {
-
-constexpr int kMaxLds = 160 * 1024;  // gfx950: 160 KiB per workgroup
-constexpr int kCtrlBytes = 1440;     // control block (PsoShared + compaction counters)
-
-// LDS layout shared by every kernel.
-//   bitmap form: [ctrl | header | bitmap | mean | (ab | cd) | (chol) | points | region]
-//                header..chol are contiguous exactly as in the HBM image
-//   dense form : [u16 cell table @0 | ctrl | dense records (cap+1, blocks of 16 means + 16 factors) | header | points | region]
-//   dense form of the fp64 score: [ctrl | records (cap+1) x 48 B | u16 cell table | header | points | region]
-//                (records first: their LDS byte addresses are the table's u16 entries)
-//   region = max(table-build scratch {key, cellkey, cnt, bm2, plist, (bm)}, swarm)
-struct Layout {
-  int ctrl_off, hdr_off, bm_off, mean_off, ab_off, cd_off, chol_off, drec_off, pts_off, region_off, total;
-  int key_off, cellkey_off, cnt_off, bm2_off, plist_off;  // build scratch inside region
-  int swarm_global;  // 1: the swarm does not fit in LDS and lives in an HBM workspace (large-swarm configs)
-  int xs_off, xs_slots;  // exact mode: partial-sum scratch of the arbitration, xs_slots x 512 bytes (exact_tasks_wg); -1: none
-  int dtab_off;          // fp64 score on the dense table (PATH 8 / 9): the u16 cell table; -1: none
-};
-
-// fmt: kScoreF32 -> mean+chol, kScoreF64 -> mean+ab+cd, 2 -> everything (table build kernel);
-// ddw > 0: dense form with a ddw x ddh cell table (fp32 score only)
-Layout make_layout(int n_words, int rec_cap, int n_max, int P, int fmt, int ddw = 0, int ddh = 0,
-                   bool swarm_global = false, bool exact = false, bool exact_units = false) {
-  Layout L;
-  L.swarm_global = swarm_global ? 1 : 0;
-  const bool dense = ddw > 0, d64 = dense && fmt == kScoreF64;
-  int off = (dense && !d64) ? dense_tab_bytes(ddw, ddh) : 0;
-  L.ctrl_off = off;
-  off += kCtrlBytes;
-  L.drec_off = -1;
-  L.dtab_off = -1;
-  if (d64) {
-    L.drec_off = off;
-    off += align16(d64_rec_bytes(rec_cap + 1));
-    L.dtab_off = off;
-    off += dense_tab_bytes(ddw, ddh);
-  } else if (dense) {
-    L.drec_off = off;
-    off += dense_rec_bytes(rec_cap + 1);
-  }
-  L.hdr_off = off;
-  off += kImageHeaderBytes;
-  L.bm_off = L.mean_off = L.ab_off = L.cd_off = L.chol_off = -1;
-  if (!dense) {
-    L.bm_off = off;
-    off += align16(n_words * 8);
-    L.mean_off = off;
-    off += 16 * rec_cap;
-    if (fmt == kScoreF64 || fmt == 2) {
-      L.ab_off = off;
-      L.cd_off = off + 16 * rec_cap;
-      off += 32 * rec_cap;
-    }
-    if (fmt == kScoreF32 || fmt == 2) {
-      L.chol_off = off;
-      off += 16 * rec_cap;
-    }
-  }
-  L.pts_off = off;
-  off += round_up(n_max, kPointPad) * 16;
-  L.region_off = off;
-  const int ints = align16(n_max * 4);
-  L.key_off = L.region_off;
-  L.cellkey_off = L.key_off + ints;
-  L.cnt_off = L.cellkey_off + ints;
-  L.bm2_off = L.cnt_off + ints;
-  L.plist_off = L.bm2_off + align16(n_words * 8);
-  int scratch = 3 * ints + align16(n_words * 8) + align16(n_max * 2);
-  if (dense) {  // the built-cell bitmap is only needed while the table is being built
-    L.bm_off = L.region_off + scratch;
-    scratch += align16(n_words * 8);
-  }
-  const int swarm = (P > 0 && !swarm_global) ? swarm_bytes(P, exact, swarm_has_raw2(P, false)) : 0;
-  L.total = L.region_off + std::max(scratch, swarm);
-  L.xs_off = -1;
-  L.xs_slots = 0;
-  // The fused pairs kernels with the swarm in LDS split the arbitration's fp64 scores into units; a single alignment's
-  // kernels and the kernels of swarms kept in HBM score whole tasks per wave (the arbitration is 1 % of their time).
-  // The unit form on the HBM-swarm kernels is what rounds 3 and 4 saw return wrong poses in some builds: not a matter of
-  // the workgroup size (round 3's reading) but of the callers' code around the two out-of-line scoring functions under
-  // interprocedural register allocation -- six builds made with it fail identically, the same sources without it pass
-  // (NOTEBOOK, "The unit form on swarms kept in HBM") -- and the library is built without IPRA since (build.py).
-  // tests/test_gpu_fullsize.py::test_unit_form_on_swarms_kept_in_hbm keeps running those kernels WITH units
-  // (NDTPSO_UNITS_HBM=<slots>, tests only) against the fp64 mode in every build.
-  static const int units_hbm = [] {  // tests only: scratch slots of the unit form for swarms kept in HBM (0: whole tasks)
-    const char* e = std::getenv("NDTPSO_UNITS_HBM");
-    // (a task's four units take four consecutive slots: a multiple of four, at most 64)
-    return e ? std::min(std::max(std::atoi(e), 0) & ~3, 64) : 0;
-  }();
-  if (exact && exact_units && (!swarm_global || units_hbm > 0)) {
-    L.xs_slots = swarm_global ? units_hbm : 8;  // one unit per wave of the workgroup
-    L.xs_off = L.total;
-    L.total += L.xs_slots * kWave * 8;
-  }
-  return L;
-}
-
-DenseP make_dense(const GridP& g, const WinP& wn, const Layout& L) {
-  DenseP d;
-  d.clip = ((double)g.W * g.cs - 2. * g.hw > 1e-9 * g.hw || (double)g.H * g.cs - 2. * g.hh > 1e-9 * g.hh) ? 1 : 0;
-  d.dw = wn.w + 1;
-  d.dh = wn.h + 1;
-  d.ox = wn.x0 - 1;
-  d.oy = wn.y0 - 1;
-  d.rec_off = L.drec_off;
-  dense_set_limits(d, g.hw, g.hh, g.inv_cs);
-  return d;
-}
-
-}  // namespace
-
-static_assert(sizeof(PsoShared) + 32 * sizeof(int) <= kCtrlBytes, "control block too small");
-
-// cluster kernels run at most 8 waves per workgroup (cluster_shape), which leaves each wave 256 VGPRs
-constexpr int kClusterMaxThreads = 512;
-
-extern __shared__ __attribute__((aligned(16))) unsigned char g_lds[];
-
-__device__ __forceinline__ PsoShared* lds_ctrl(int ctrl_off) { return reinterpret_cast<PsoShared*>(g_lds + ctrl_off); }
-__device__ __forceinline__ int* lds_cnt(int ctrl_off) {
-  return reinterpret_cast<int*>(g_lds + ctrl_off + sizeof(PsoShared));
-}
-
-__device__ __forceinline__ void copy16(void* dst, const void* src, int bytes) {
-  // bytes is a multiple of 16; 16 B per lane, consecutive lanes consecutive addresses (coalesced)
-  const uint4* s = reinterpret_cast<const uint4*>(src);
-  uint4* d = reinterpret_cast<uint4*>(dst);
-  for (int i = threadIdx.x; i < (bytes >> 4); i += blockDim.x) d[i] = s[i];
-}
-
-__device__ __forceinline__ TableView lds_table_view(const Layout& L) {
-  TableView T;
-  T.bm = L.bm_off >= 0 ? reinterpret_cast<const uint2*>(g_lds + L.bm_off) : nullptr;
-  T.mean = L.mean_off >= 0 ? reinterpret_cast<const double2*>(g_lds + L.mean_off) : nullptr;
-  T.ab = L.ab_off >= 0 ? reinterpret_cast<const double2*>(g_lds + L.ab_off) : nullptr;
-  T.cd = L.cd_off >= 0 ? reinterpret_cast<const double2*>(g_lds + L.cd_off) : nullptr;
-  T.chol = L.chol_off >= 0 ? reinterpret_cast<const float4*>(g_lds + L.chol_off) : nullptr;
-  return T;
-}
-__device__ __forceinline__ TableOut lds_table_out(const Layout& L) {
-  TableOut T;
-  T.bm = reinterpret_cast<uint2*>(g_lds + L.bm_off);
-  T.mean = L.mean_off >= 0 ? reinterpret_cast<double2*>(g_lds + L.mean_off) : nullptr;
-  T.ab = L.ab_off >= 0 ? reinterpret_cast<double2*>(g_lds + L.ab_off) : nullptr;
-  T.cd = L.cd_off >= 0 ? reinterpret_cast<double2*>(g_lds + L.cd_off) : nullptr;
-  T.chol = L.chol_off >= 0 ? reinterpret_cast<float4*>(g_lds + L.chol_off) : nullptr;
-  return T;
-}
-__device__ __forceinline__ EvalCtx make_eval_ctx(const GridP& g, const WinP& wn, const Layout& L, const DenseP& dn) {
-  EvalCtx E;
-  E.g = g;
-  E.wn = wn;
-  E.T = lds_table_view(L);
-  E.dn = dn;
-  E.lds0 = g_lds;
-  E.light = 0;
-  E.guard_lds = 0;
-  E.d64_tab = 0;
-  return E;
-}
-
-// bitmap-form table views into an image in HBM: [header | bitmap | mean | ab | cd | chol]
-__device__ __forceinline__ TableView image_table_view(const WinP& wn, const unsigned char* __restrict__ image) {
-  TableView T;
-  T.bm = reinterpret_cast<const uint2*>(image + kImageHeaderBytes);
-  T.mean = reinterpret_cast<const double2*>(image + image_mean_offset(wn.n_words));
-  T.ab = reinterpret_cast<const double2*>(image + image_ab_offset(wn.n_words, wn.rec_cap));
-  T.cd = reinterpret_cast<const double2*>(image + image_cd_offset(wn.n_words, wn.rec_cap));
-  T.chol = reinterpret_cast<const float4*>(image + image_chol_offset(wn.n_words, wn.rec_cap));
-  return T;
-}
-// exact mode (fp32-score dense kernels): the fp64 table the arbitration reads, where its image lies in HBM, goes into
-// the LDS parameter block of exact_tasks (thread 0 writes; the barriers of the swarm initialisation publish it)
-template <bool BYTE>
-__device__ __forceinline__ void enable_arbitration(PsoShared* sh, const GridP& g, const WinP& wn, const DenseP& dn,
-                                                   const unsigned char* __restrict__ image, const Layout& L) {
-  if (threadIdx.x == 0) {
-    ExactArgs& a = sh->xa;
-    a.xs_lds = L.xs_slots ? (unsigned)(uintptr_t)(const unsigned char __attribute__((address_space(3)))*)(g_lds + L.xs_off) : 0u;
-    a.xs_slots = L.xs_slots;
-    a.g = g;
-    a.dw = dn.dw;
-    a.dh = dn.dh;
-    a.ox = dn.ox;
-    a.oy = dn.oy;
-    a.null_entry = BYTE ? (unsigned)dn.rec_off : (unsigned)dn.rec_off >> 4;
-    const TableView T = image_table_view(wn, image);
-    a.xmean = T.mean;
-    a.xab = T.ab;
-    a.xcd = T.cd;
-  }
-}
-
-// the table image where it lies in HBM, for maps whose table does not fit in LDS (PATH 4 / 5)
-__device__ __forceinline__ EvalCtx make_eval_ctx_global(const GridP& g, const WinP& wn, const DenseP& dn,
-                                                        const unsigned char* __restrict__ image) {
-  EvalCtx E;
-  E.g = g;
-  E.wn = wn;
-  E.T = image_table_view(wn, image);
-  E.dn = dn;
-  E.lds0 = g_lds;
-  E.light = 0;
-  E.guard_lds = 0;
-  E.d64_tab = 0;
-  return E;
-}
-
-// stage a table image (HBM) into LDS in the form the kernel's PATH wants
-template <int MODE, int PATH>
-__device__ __forceinline__ void stage_image(const unsigned char* __restrict__ image, const GridP& g, const WinP& wn,
-                                            const Layout& L, const DenseP& dn) {
-  if constexpr (PATH >= 4) {  // table stays in HBM (served by L2); only the header is staged
-    copy16(g_lds + L.hdr_off, image, kImageHeaderBytes);
-  } else if constexpr (PATH == 2) {
-    copy16(g_lds + L.hdr_off, image, kImageHeaderBytes);
-    dense_from_image_wg(g, wn, image, dn, g_lds);
-  } else if constexpr (MODE == kScoreF64) {
-    copy16(g_lds + L.hdr_off, image, image_chol_offset(wn.n_words, wn.rec_cap));  // header .. cd, contiguous
-  } else {
-    copy16(g_lds + L.hdr_off, image, image_ab_offset(wn.n_words, wn.rec_cap));  // header .. mean
-    copy16(g_lds + L.chol_off, image + image_chol_offset(wn.n_words, wn.rec_cap), 16 * wn.rec_cap);
-  }
-}
+#include "ndtpso_device_common.inc"
+#include "ndtpso_align_jobs.h"
 
 // ---- K3a -------------------------------------------------------------------------------------
 __global__ void __launch_bounds__(1024)
@@ -451,13 +223,6 @@ k_cost_batch(const unsigned char* __restrict__ image, const double2* __restrict_
 }
 
 // ---- K2 --------------------------------------------------------------------------------------
-// the last store of a result a kernel leaves in pinned host memory: everything this thread wrote before it is visible to
-// the host that reads the word
-__device__ __forceinline__ void publish_pinned_word(uint32_t* word, uint32_t value) {
-  __threadfence_system();
-  __hip_atomic_store(word, value, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
-}
-
 // CLUSTER: gridDim.x workgroups share this one alignment (see ClusterP in ndtpso_kernels.hpp)
 template <int MODE, int PATH, bool CLUSTER, bool ARB = false>
 __global__ void __launch_bounds__(CLUSTER ? kClusterMaxThreads : 1024)
@@ -475,83 +240,7 @@ k_align(const unsigned char* __restrict__ image, const double2* __restrict__ xy,
   } else {
     cl.rank = 0;
   }
-  if (CLUSTER && cl.rank == cl.absent) return;
-  // The rand() table in a pinned HOST slot (table_src; ndtpso_map_align): fetched in one sweep into this workgroup's
-  // own copy in HBM, the loads in flight together -- one trip over the host link instead of a copy operation ahead of
-  // the kernel.  (Read in place, an iteration's draws one iteration ahead, the trips were not hidden: the memory counter
-  // retires in order, so every later load waited for them; 66 us per alignment.)  The first reader comes after the
-  // barrier below.
-  const int32_t* draws_table = table;
-  if (table_src) {
-    int4* dst = table_dst + (size_t)cl.rank * (size_t)table_vec;
-    for (int q = (int)threadIdx.x; q < table_vec; q += (int)blockDim.x) dst[q] = table_src[q];
-    draws_table = reinterpret_cast<const int32_t*>(dst);
-  }
-  if (threadIdx.x == 0 && cl.rank == 0 && stats) *stats = AlignStats{0, 0, 0, 0, 0, 0, 0, 0};  // only this workgroup writes it
-  if constexpr (PATH == 2) {
-    if (late_hdr) {  // late window binding (AlignSrc::late_hdr): uniform, and the same in every workgroup of a cluster
-      const int nb = (int)late_hdr[1], x0 = (int)late_hdr[4], x1 = (int)late_hdr[5], y0 = (int)late_hdr[6], y1 = (int)late_hdr[7];
-      wn.x0 = x0;
-      wn.y0 = y0;
-      wn.w = x1 - x0 + 1;
-      wn.h = y1 - y0 + 1;
-      wn.n_words = (int)late_hdr[3];
-      wn.rec_cap = max(nb, 1);
-      dn.dw = wn.w + 1;
-      dn.dh = wn.h + 1;
-      dn.ox = x0 - 1;
-      dn.oy = y0 - 1;
-      dense_set_limits(dn, g.hw, g.hh, g.inv_cs);
-      if (dense_entries(dn.dw, dn.dh) > late_table_cap || wn.rec_cap > late_rec_cap) {
-        if (threadIdx.x == 0 && cl.rank == 0 && stats) {
-          stats->status = kStatusLateOverflow;
-          if (mirror) {
-            reinterpret_cast<AlignStats*>(mirror + 4)->status = kStatusLateOverflow;
-            publish_pinned_word(reinterpret_cast<uint32_t*>(mirror + 8), seq);
-          }
-        }
-        return;
-      }
-    }
-  }
-  if (n_ptr) n = min((int)*n_ptr, n);  // the point count lives on the device (resident scan); n is its capacity
-  double2* pts = reinterpret_cast<double2*>(g_lds + L.pts_off);
-  stage_image<MODE, PATH>(image, g, wn, L, dn);
-  copy16(pts, xy, n * 16);
-  pad_points_wg(pts, n);
-  __syncthreads();
-  EvalCtx E = PATH >= 4 ? make_eval_ctx_global(g, wn, dn, image) : make_eval_ctx(g, wn, L, dn);
-  E.light = CLUSTER ? 0 : ps.light;
-  if constexpr (ARB) enable_arbitration<PATH == 3>(lds_ctrl(L.ctrl_off), g, wn, dn, image, L);  // exact mode: the staged image holds the fp64 records
-  // a swarm too large for LDS lives in an HBM workspace, one per workgroup of a cluster (each keeps the whole swarm)
-  // Two copies of the PSO, one per home of the swarm, so that in each the compiler knows the address space of the
-  // swarm arrays: selecting the base pointer at run time made every swarm access a FLAT instruction (74 of them), and
-  // the proposal / commit phases -- one or two waves working, the rest waiting -- are chains of exactly those accesses.
-  if (L.swarm_global) {
-    const Swarm sw = swarm_carve(ws + (size_t)cl.rank * swarm_bytes(ps.P, true, true), ps.P, ARB, true);
-    pso_run_wg<MODE, PATH, CLUSTER, ARB, false, true>(E, pts, n, ps, guess, dev, seed, draws_table, sw, lds_ctrl(L.ctrl_off), out_pose,
-                                         out_cost, stats, cl);
-  } else {
-    const Swarm sw = swarm_carve(g_lds + L.region_off, ps.P, ARB, swarm_has_raw2(ps.P, false));
-    pso_run_wg<MODE, PATH, CLUSTER, ARB>(E, pts, n, ps, guess, dev, seed, draws_table, sw, lds_ctrl(L.ctrl_off), out_pose,
-                                         out_cost, stats, cl);
-  }
-  if (threadIdx.x == 0 && stats && cl.rank == 0) {
-    const ImageHeader* h = reinterpret_cast<const ImageHeader*>(g_lds + L.hdr_off);
-    stats->n_built = h->n_built;
-    stats->status = (stats->status & (kStatusNeedsF64 | kStatusClusterTimeout | 0xffff0000u)) | h->status;
-    // the host's copy of {pose, cost, statistics}: written into its pinned slot from here (this thread wrote all of it),
-    // so that no copy operation stands between the end of the kernel and the host's wake-up
-    if (mirror) {
-      static_assert(sizeof(AlignStats) == 32, "result slot layout");
-#pragma unroll
-      for (int k = 0; k < 4; ++k) mirror[k] = out_pose[k];  // [3] is the cost's place (out_cost, when wanted)
-      const double* sd = reinterpret_cast<const double*>(stats);
-#pragma unroll
-      for (int k = 0; k < 4; ++k) mirror[4 + k] = sd[k];
-      publish_pinned_word(reinterpret_cast<uint32_t*>(mirror + 8), seq);  // the host polls this word (wait_pinned_word)
-    }
-  }
+#include "ndtpso_align_body.inc"
 }
 
 // The guard of the one-workgroup dense kernels when the box of scan B's DISC does not fit the table beside scan A's (cells of
@@ -923,6 +612,12 @@ struct ndtpso_ctx {
   int fb_big_calls = 0;  // calls since the largest table was put first (it is tried without every 64 calls)
   void* result_pinned = nullptr;      // pinned landing slot of one alignment's pose / cost / statistics (align_once)
   hipEvent_t result_event = nullptr;
+  // ndtpso_map_align_batch: one pinned result slot per job of a launch (kJobSlotBytes each), the device's copies of the results
+  // and of the staged rand() tables, and the jobs' numbers -- a counter of its own: the slots are not the single path's
+  void* jobs_pinned = nullptr;
+  size_t jobs_pinned_cap = 0;
+  DevBuf jobs_out, jobs_table;
+  uint32_t jobs_issued = 0;
 };
 
 namespace {
@@ -1249,6 +944,7 @@ int check_pso(ndtpso_ctx* ctx, const ndtpso_pso_config* cfg) {
 }
 
 int exact_mode_resolve(ndtpso_ctx* c, int* mode);  // ndtpso_selftest.inc: the start-up check of NDTPSO_SCORE_EXACT
+int exact_jobs_resolve(ndtpso_ctx* c, int asked, int* mode);  // ... and its second part, the arbitrating job kernels (ndtpso_map_align_batch)
 
 }  // namespace
 
@@ -1319,6 +1015,7 @@ int ndtpso_ctx_create(int device, ndtpso_ctx** out) {
   if (e == hipSuccess) e = allow_big_lds(k_align_pairs<kScoreF64, 9, false, false, false, 2, true>);
   if (e == hipSuccess) e = allow_big_lds(k_align<kScoreF32, 2, false, true>);
   if (e == hipSuccess) e = allow_big_lds(k_align<kScoreF32, 2, true, true>);
+  if (e == hipSuccess) e = align_jobs_allow_big_lds();  // the job kernels (ndtpso_map_align_batch; ndtpso_align_jobs.hip)
 #define GLOBAL_PATHS(K, ...)                                                   \
   if (e == hipSuccess) e = allow_big_lds(K<kScoreF32, 4 __VA_ARGS__>);         \
   if (e == hipSuccess) e = allow_big_lds(K<kScoreF32, 5 __VA_ARGS__>);         \
@@ -1348,7 +1045,7 @@ void ndtpso_ctx_destroy(ndtpso_ctx* c) {
   (void)hipSetDevice(c->device);
   (void)hipStreamSynchronize(c->stream);
   for (DevBuf* b : {&c->image, &c->rows, &c->xy, &c->xy2, &c->ranges, &c->ranges2, &c->poses, &c->costs, &c->dump,
-                    &c->small, &c->table, &c->out, &c->seeds, &c->ws, &c->gate, &c->cluster_xc, &c->ximg})
+                    &c->small, &c->table, &c->out, &c->seeds, &c->ws, &c->gate, &c->cluster_xc, &c->ximg, &c->jobs_out, &c->jobs_table})
     b->release();
   for (BeamDirs& b : c->beam_dirs) b.buf.release();
   c->pinned.release();
@@ -1363,6 +1060,7 @@ void ndtpso_ctx_destroy(ndtpso_ctx* c) {
   if (c->pipe_in) (void)hipEventDestroy(c->pipe_in);
   if (c->result_event) (void)hipEventDestroy(c->result_event);
   if (c->result_pinned) (void)hipHostFree(c->result_pinned);
+  if (c->jobs_pinned) (void)hipHostFree(c->jobs_pinned);
   if (c->pairs_fb) (void)hipHostFree(c->pairs_fb);
   if (c->own_stream) (void)hipStreamDestroy(c->own_stream);
   delete c;

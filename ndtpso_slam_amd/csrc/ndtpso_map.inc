@@ -1229,6 +1229,12 @@ int ndtpso_map_align(ndtpso_map* m, const ndtpso_points* pts, const double guess
   return align_finish(c, src, cfg, seed, rand_table != nullptr, mode, out_pose, out_cost, stats, og);
 }
 
+}  // extern "C"
+
+#include "ndtpso_map_batch.inc"
+
+extern "C" {
+
 // cost_function (core.cpp:26-48) of the points of a loaded scan against the map, for m poses; builds first if points
 // were inserted since the last build, like the reference.  Synchronous.
 int ndtpso_map_cost(ndtpso_map* m, ndtpso_points* pts, const double* poses, uint32_t n_poses, int mode, double* costs) {

@@ -369,6 +369,163 @@ int exact_mode_resolve(ndtpso_ctx* c, int* mode) {
   return NDTPSO_OK;
 }
 
+
+// ---- ... and of the arbitrating job kernels (ndtpso_map_align_batch) ---------------------------------------------------------
+// k_align_jobs<F32, 2, one workgroup / cluster, ARB> are two more callers of the arbitration's out-of-line scores, so the rule
+// holds for them too: checked before trusted.  A second table beside kExactFamilies (which, with its budget, stays as it is), run
+// the first time a process asks ndtpso_map_align_batch for the exact mode on a device: the same fixed problem as a resident map
+// and four jobs of one launch, each family forced (PlanForce::cluster) and confirmed by the instantiation the launch recorded
+// (kLaunchJobForm), compared bit for bit with the fp64 mode's single alignments.  A family that fails refuses the exact mode to
+// the batch entry only: its exact-mode jobs run the fp64 score, and ndtpso_last_error says why.
+struct ExactJobFamily {
+  const char* name;
+  int cluster;    // PlanForce::cluster of the family
+  uint32_t code;  // launch_code() | kLaunchJobForm of the instantiation it must reach
+};
+const ExactJobFamily kExactJobFamilies[] = {
+    {"jobs of one launch, one workgroup each (ndtpso_map_align_batch)", 0, launch_code(false, 2, false, true, false, 0, false, false) | kLaunchJobForm},
+    {"jobs of one launch, a cluster of workgroups each (ndtpso_map_align_batch)", 1, launch_code(false, 2, true, true, false, 0, false, false) | kLaunchJobForm},
+};
+constexpr int kExactJobFamilyCount = (int)(sizeof(kExactJobFamilies) / sizeof(kExactJobFamilies[0]));
+
+struct ExactJobsCheck {
+  std::mutex mu;
+  std::atomic<int> state{0};  // 0 not run, 1 passed, 2 refused
+  int attempts = 0;
+  bool ran = false;           // fam[] holds a run's results
+  std::string why;
+  double ms = 0.;
+  ExactFamilyResult fam[kExactJobFamilyCount];
+};
+ExactJobsCheck g_exact_jobs_check[64];
+
+bool run_exact_jobs_check(int device, ExactJobsCheck& ec) {
+  const auto t0 = std::chrono::steady_clock::now();
+  auto no_verdict = [&](const std::string& why) {
+    ec.why = "the check of NDTPSO_SCORE_EXACT's job kernels could not run on device " + std::to_string(device) +
+             " (this call's jobs run the fp64 score, the next one tries again): " + why;
+    return false;
+  };
+  for (ExactFamilyResult& r : ec.fam) r = ExactFamilyResult{};
+  ndtpso_ctx* t = nullptr;
+  if (ndtpso_ctx_create(device, &t) != NDTPSO_OK) return no_verdict("no context for the check");
+  struct Guard {
+    ndtpso_ctx* t;
+    ndtpso_map* map = nullptr;
+    ndtpso_points *a = nullptr, *b = nullptr;
+    ~Guard() {
+      if (map) ndtpso_map_destroy(map);
+      if (a) ndtpso_points_destroy(a);
+      if (b) ndtpso_points_destroy(b);
+      ndtpso_ctx_destroy(t);
+    }
+  } gd{t};
+  constexpr int kBeams = 181, kJobs = 4;
+  const ndtpso_scan_geom geom{(uint32_t)kBeams, -2.356194f, 4.712389f / 180.f, 20.f, 0.1f};
+  const ndtpso_grid grid{40, 40, 0.5};
+  ndtpso_pso_config cfg{20, 24, -1, 0.8, 2., 2., 1.};
+  const double dev3[3] = {3e-5, 3e-5, 1e-6}, zero3[3] = {0., 0., 0.};  // (run_exact_check: comparisons ARE arbitrated)
+  std::vector<float> ra(kBeams), rb(kBeams);
+  kat_scan(0.3, 0., 0., 0u, kBeams, geom.min_angle, geom.angle_increment, ra.data());  // (pair 0 of run_exact_check's batch)
+  kat_scan(0.3 + 0.04, 0., 0.008, 1u, kBeams, geom.min_angle, geom.angle_increment, rb.data());
+  int rc = ndtpso_points_create(t, kBeams, &gd.a);
+  if (rc == NDTPSO_OK) rc = ndtpso_points_create(t, kBeams, &gd.b);
+  if (rc == NDTPSO_OK) rc = ndtpso_map_create(t, &grid, 0., 4u << 20, &gd.map);
+  if (rc == NDTPSO_OK) rc = ndtpso_points_load_scan(gd.a, ra.data(), &geom, zero3, nullptr, 0);
+  if (rc == NDTPSO_OK) rc = ndtpso_points_load_scan(gd.b, rb.data(), &geom, zero3, nullptr, 0);
+  if (rc == NDTPSO_OK) rc = ndtpso_map_insert(gd.map, gd.a, zero3);
+  if (rc == NDTPSO_OK) rc = ndtpso_map_build(gd.map);
+  if (rc != NDTPSO_OK) return no_verdict(std::string("the check's map failed: ") + ndtpso_last_error(t));
+  double p64[kJobs][3], c64[kJobs];
+  for (int j = 0; j < kJobs; ++j) {
+    ndtpso_align_stats st;
+    rc = ndtpso_map_align(gd.map, gd.b, zero3, dev3, &cfg, 1u + (uint32_t)j, nullptr, NDTPSO_SCORE_F64, p64[j], &c64[j], &st);
+    if (rc != NDTPSO_OK) return no_verdict(std::string("the check's fp64 alignment failed: ") + ndtpso_last_error(t));
+  }
+  std::string first_bad;
+  for (int f = 0; f < kExactJobFamilyCount; ++f) {
+    const ExactJobFamily& fam = kExactJobFamilies[f];
+    ExactFamilyResult& r = ec.fam[f];
+    r.units = kJobs;
+    ndtpso_map_align_job jobs[kJobs];
+    std::memset(jobs, 0, sizeof(jobs));
+    for (int j = 0; j < kJobs; ++j) {
+      jobs[j].map = gd.map;
+      jobs[j].new_points = gd.b;
+      for (int k = 0; k < 3; ++k) jobs[j].deviation[k] = dev3[k];
+      jobs[j].seed = 1u + (uint32_t)j;
+      jobs[j].flags = 1u;
+    }
+    {
+      PlanForce force;
+      force.cluster = fam.cluster;
+      ForceScope scope(force);
+      t_last_launch = 0;
+      rc = ndtpso_map_align_batch(t, jobs, kJobs, &cfg, NDTPSO_SCORE_EXACT);
+      r.launched = t_last_launch;
+    }
+    if (rc != NDTPSO_OK) return no_verdict(std::string("the check's launch (") + fam.name + ") failed: " + ndtpso_last_error(t));
+    if (r.launched != fam.code) {  // (too few compute units for a cluster per job, ...: what the entry cannot reach here it cannot run here)
+      r.state = 3;
+      continue;
+    }
+    for (int j = 0; j < kJobs; ++j) {
+      r.arbitrated += NDTPSO_STATUS_ARBITRATED(jobs[j].stats.status);
+      r.mismatched += jobs[j].route < 1 || !same_bits(jobs[j].pose, p64[j], 3) || !same_bits(&jobs[j].cost, &c64[j], 1);
+    }
+    r.state = (r.mismatched == 0 && r.arbitrated > 0) ? 1 : 2;
+    if (r.state == 2 && first_bad.empty())
+      first_bad = r.mismatched ? std::string("poses or costs of ") + std::to_string(r.mismatched) + " of " + std::to_string(r.units) +
+                                     " jobs of the family \"" + fam.name + "\" differ from the fp64 mode's (miscompiled arbitration? see ndtpso_slam_amd/build.py)"
+                               : std::string("the family \"") + fam.name + "\" arbitrated no comparison: it no longer exercises what it is there for";
+  }
+  ec.ms = 1e3 * std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+  ec.ran = true;
+  if (!first_bad.empty()) {
+    ec.why = "NDTPSO_SCORE_EXACT refused to ndtpso_map_align_batch on device " + std::to_string(device) +
+             " (its exact-mode jobs run the fp64 score instead): " + first_bad;
+    ec.state.store(2);
+    return true;
+  }
+  ec.why.clear();
+  ec.state.store(1);
+  return true;
+}
+
+// The batch entry was asked for NDTPSO_SCORE_EXACT (`asked`; *mode is what exact_mode_resolve made of it): the exact mode only
+// where the job kernels have passed too.  The check runs whatever the start-up check said, so that the report is complete.
+int exact_jobs_resolve(ndtpso_ctx* c, int asked, int* mode) {
+  if (!c || asked != NDTPSO_SCORE_EXACT || t_in_exact_check) return NDTPSO_OK;
+  static const bool skip = [] {
+    const char* e = std::getenv("NDTPSO_EXACT_CHECK");
+    return e && e[0] == '0';
+  }();
+  if (skip) return NDTPSO_OK;
+  ExactJobsCheck& ec = g_exact_jobs_check[c->device & 63];
+  if (ec.state.load(std::memory_order_acquire) == 1) return NDTPSO_OK;
+  std::lock_guard<std::mutex> lock(ec.mu);
+  if (ec.state.load() == 0) {
+    t_in_exact_check = true;
+    const PlanForce keep = t_plan_force;
+    const uint32_t keep_launch = t_last_launch;
+    const bool verdict = run_exact_jobs_check(c->device, ec);
+    t_plan_force = keep;
+    t_last_launch = keep_launch;
+    t_in_exact_check = false;
+    if (!verdict && ++ec.attempts >= 3) {
+      ec.why += " -- third failure: the mode stays refused";
+      ec.state.store(2);
+    }
+    if (ec.state.load() == 2 || !verdict) std::fprintf(stderr, "ndtpso: %s\n", ec.why.c_str());
+    (void)hipSetDevice(c->device);
+  }
+  if (ec.state.load() != 1) {
+    c->err = ec.why;
+    *mode = NDTPSO_SCORE_F64;
+  }
+  return NDTPSO_OK;
+}
+
 }  // namespace
 
 extern "C" int ndtpso_exact_check(ndtpso_ctx* c, int* state, uint32_t* arbitrated_batch, uint32_t* arbitrated_single, double* ms) {
@@ -402,6 +559,18 @@ extern "C" int ndtpso_exact_check_report(ndtpso_ctx* c, char* buf, uint32_t cap)
          ", \"alignments\": " + std::to_string(r.units) + ", \"arbitrated\": " + std::to_string(r.arbitrated) +
          ", \"mismatched\": " + std::to_string(r.mismatched) + "}";
   }
+  s += "], \"job_families\": [";  // the job kernels' families (exact_jobs_resolve): empty until that check has run
+  {
+    ExactJobsCheck& jc = g_exact_jobs_check[c->device & 63];
+    std::lock_guard<std::mutex> jlock(jc.mu);
+    for (int f = 0; jc.ran && f < kExactJobFamilyCount; ++f) {
+      const ExactFamilyResult& r = jc.fam[f];
+      s += std::string(f ? ", " : "") + "{\"name\": \"" + kExactJobFamilies[f].name + "\", \"state\": \"" + names[r.state & 3] +
+           "\", \"instantiation\": " + std::to_string(kExactJobFamilies[f].code) + ", \"launched\": " + std::to_string(r.launched) +
+           ", \"alignments\": " + std::to_string(r.units) + ", \"arbitrated\": " + std::to_string(r.arbitrated) +
+           ", \"mismatched\": " + std::to_string(r.mismatched) + "}";
+    }
+  }
   s += "]}";
   if (buf && cap) {
     const size_t n = std::min<size_t>(s.size(), cap - 1);
@@ -409,4 +578,17 @@ extern "C" int ndtpso_exact_check_report(ndtpso_ctx* c, char* buf, uint32_t cap)
     buf[n] = 0;
   }
   return (int)s.size();
+}
+
+// Runs the check of the arbitrating job kernels if it has not run (after the start-up check itself): state 1 passed, 2 refused,
+// 0 no verdict (the exact mode is refused to the device altogether, the check is switched off, or it could not run).
+extern "C" int ndtpso_exact_check_jobs(ndtpso_ctx* c, int* state) {
+  if (!c) return NDTPSO_E_ARG;
+  int mode = NDTPSO_SCORE_EXACT;
+  if (int rc = exact_mode_resolve(c, &mode)) return rc;
+  if (int rc = exact_jobs_resolve(c, NDTPSO_SCORE_EXACT, &mode)) return rc;
+  ExactJobsCheck& ec = g_exact_jobs_check[c->device & 63];
+  std::lock_guard<std::mutex> lock(ec.mu);
+  if (state) *state = ec.state.load();
+  return NDTPSO_OK;
 }
