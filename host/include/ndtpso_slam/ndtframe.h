@@ -139,6 +139,11 @@ class NDTFrame {
   bool s_last_align_ok{true};
   void append(const double* xy, const int32_t* idx, uint32_t n);
   bool uploadTable();  // false: the device refused the table (error recorded, see status.h)
+  // what align() does around its alignment, step by step (alignBatch does the same steps around a shared launch)
+  Vector3d nextDeviation();                 // the search range of this frame's next alignment; counts it
+  void recordAlignOutcome(bool ok);         // built, lastAlignOk(), the refusal of update() after a failure
+  Vector3d recordAlignedPose(Vector3d pose);  // the pose align() returns; s_pose_diff / s_prev_pose follow it
+  struct DeviceScan;  // a new frame's points as an ndtpso_points (ndtframe.cpp)
   // resident mode
   bool s_resident{false};
   ndtpso_points* d_scan_{nullptr};  // a one-cell frame that only ever had scans loaded: its point list

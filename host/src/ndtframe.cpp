@@ -482,6 +482,39 @@ bool NDTFrame::uploadTable() {
   return true;
 }
 
+// A new frame's points as an ndtpso_points of the active context: the frame's resident scan in place, or a pooled temporary
+// scan filled through the host (`foreign`: a frame of another thread's context, its points already collected) and released
+// with this object.
+struct NDTFrame::DeviceScan {
+  ndtpso_points* pts = nullptr;
+  DeviceScan(const NDTFrame* f, bool is_foreign, std::vector<double>& foreign, const char* what) {
+    if (!is_foreign && f->s_resident && f->d_scan_ && !f->d_map_) {
+      pts = f->d_scan_;
+      return;
+    }
+    std::vector<double> xy;
+    if (is_foreign) xy.swap(foreign); else f->collectPoints(xy);
+    cap_ = std::max(kScanCapacity, (uint32_t)(xy.size() / 2));
+    pts = tmp_ = ndtpso_host::acquire_scan(cap_);
+    ndtpso_host::check(ndtpso_points_set(tmp_, xy.data(), (uint32_t)(xy.size() / 2)), what);
+  }
+  ~DeviceScan() {
+    if (tmp_) ndtpso_host::release_scan(tmp_, cap_);
+  }
+  DeviceScan(const DeviceScan&) = delete;
+  DeviceScan& operator=(const DeviceScan&) = delete;
+
+ private:
+  ndtpso_points* tmp_ = nullptr;
+  uint32_t cap_ = 0;
+};
+
+void NDTFrame::recordAlignOutcome(bool ok) {
+  if (ok) built = true;  // (the alignment built first if need be: cost_function's lazy build, core.cpp:27-28)
+  s_last_align_ok = ok;
+  t_last_align_failed = !ok;
+}
+
 // pso_optimization against this frame, core.cpp:50-116.  The std::rand() stream is drawn here, in the order and
 // quantity the reference consumes it (3 + 3P + 6PI), so srand() by the caller has the reference's meaning.
 Vector3d NDTFrame::optimize(const Vector3d& guess, const NDTFrame* new_frame, const Vector3d& deviation,
@@ -490,50 +523,28 @@ Vector3d NDTFrame::optimize(const Vector3d& guess, const NDTFrame* new_frame, co
   const bool is_foreign = new_frame->dev() != dev();
   if (is_foreign) new_frame->collectPoints(foreign);
   ndtpso_host::Use use(dev());
-  if (s_resident) {
-    ndtpso_map* m = ensureMap();  // ndtpso_map_align builds first if need be (cost_function's lazy build, core.cpp:27-28)
-    const ndtpso_points* pts = nullptr;
-    ndtpso_points* tmp = nullptr;
-    uint32_t tmp_cap = 0;
-    if (!is_foreign && new_frame->s_resident && new_frame->d_scan_ && !new_frame->d_map_) {
-      pts = new_frame->d_scan_;
-    } else {
-      std::vector<double> xy;
-      if (is_foreign) xy.swap(foreign); else new_frame->collectPoints(xy);
-      tmp_cap = std::max(kScanCapacity, (uint32_t)(xy.size() / 2));
-      tmp = ndtpso_host::acquire_scan(tmp_cap);
-      ndtpso_host::check(ndtpso_points_set(tmp, xy.data(), (uint32_t)(xy.size() / 2)), "align");
-      pts = tmp;
-    }
-    const ndtpso_pso_config abi = to_abi(cfg);
-    std::vector<int32_t> draws(ndtpso_rand_draws(&abi));
-    ndtpso_host::draw_rand(draws.data(), draws.size());  // drawn even if the device call fails: the caller's stream moves on as it would have
-    const double g[3] = {guess.x(), guess.y(), guess.z()};
-    const double dv[3] = {deviation.x(), deviation.y(), deviation.z()};
-    double pose[3] = {g[0], g[1], g[2]};
-    const bool ok = ndtpso_host::check(ndtpso_map_align(m, pts, g, dv, &abi, 0u, draws.data(), ndtpso_host::score_mode(), pose,
-                                                        nullptr, nullptr), "align");
-    if (ok) built = true;
-    if (tmp) ndtpso_host::release_scan(tmp, tmp_cap);
-    s_last_align_ok = ok;
-    t_last_align_failed = !ok;
-    return ok ? Vector3d(pose[0], pose[1], pose[2]) : guess;  // device fault: the initial guess, never a CPU estimate
-  }
-  if (!built) build();  // core.cpp:27-28 (lazy build inside cost_function)
-  const bool table_ok = uploadTable();
-  std::vector<double> xy;
-  if (is_foreign) xy.swap(foreign); else new_frame->collectPoints(xy);
   const ndtpso_pso_config abi = to_abi(cfg);
   std::vector<int32_t> draws(ndtpso_rand_draws(&abi));
-  ndtpso_host::draw_rand(draws.data(), draws.size());
+  ndtpso_host::draw_rand(draws.data(), draws.size());  // drawn even if a device call fails: the caller's stream moves on as it would have
   const double g[3] = {guess.x(), guess.y(), guess.z()};
   const double dv[3] = {deviation.x(), deviation.y(), deviation.z()};
   double pose[3] = {g[0], g[1], g[2]};
-  s_last_align_ok = table_ok && ndtpso_host::check(ndtpso_align(ndtpso_host::device(), xy.data(), (uint32_t)(xy.size() / 2), g, dv, &abi,
-                                                               0u, draws.data(), ndtpso_host::score_mode(), pose, nullptr, nullptr), "align");
-  t_last_align_failed = !s_last_align_ok;
-  if (!s_last_align_ok) return guess;
-  return Vector3d(pose[0], pose[1], pose[2]);
+  bool ok;
+  if (s_resident) {
+    ndtpso_map* m = ensureMap();  // ndtpso_map_align builds first if need be (cost_function's lazy build, core.cpp:27-28)
+    const DeviceScan scan(new_frame, is_foreign, foreign, "align");
+    ok = ndtpso_host::check(ndtpso_map_align(m, scan.pts, g, dv, &abi, 0u, draws.data(), ndtpso_host::score_mode(), pose, nullptr, nullptr),
+                            "align");
+  } else {
+    if (!built) build();  // core.cpp:27-28 (lazy build inside cost_function)
+    const bool table_ok = uploadTable();
+    std::vector<double> xy;
+    if (is_foreign) xy.swap(foreign); else new_frame->collectPoints(xy);
+    ok = table_ok && ndtpso_host::check(ndtpso_align(ndtpso_host::device(), xy.data(), (uint32_t)(xy.size() / 2), g, dv, &abi, 0u, draws.data(),
+                                                     ndtpso_host::score_mode(), pose, nullptr, nullptr), "align");
+  }
+  recordAlignOutcome(ok);
+  return ok ? Vector3d(pose[0], pose[1], pose[2]) : guess;  // device fault: the initial guess, never a CPU estimate
 }
 
 double NDTFrame::cost(const Vector3d& trans, const NDTFrame* new_frame) {
@@ -545,24 +556,11 @@ double NDTFrame::cost(const Vector3d& trans, const NDTFrame* new_frame) {
   double c = 0.;
   if (s_resident) {
     ndtpso_map* m = ensureMap();
-    ndtpso_points* tmp = nullptr;
-    uint32_t tmp_cap = 0;
-    ndtpso_points* pts = nullptr;
-    if (!is_foreign && new_frame->s_resident && new_frame->d_scan_ && !new_frame->d_map_) {
-      pts = new_frame->d_scan_;
-    } else {
-      std::vector<double> xy;
-      if (is_foreign) xy.swap(foreign); else new_frame->collectPoints(xy);
-      tmp_cap = std::max(kScanCapacity, (uint32_t)(xy.size() / 2));
-      tmp = ndtpso_host::acquire_scan(tmp_cap);
-      ndtpso_host::check(ndtpso_points_set(tmp, xy.data(), (uint32_t)(xy.size() / 2)), "cost_function");
-      pts = tmp;
-    }
-    if (ndtpso_host::check(ndtpso_map_cost(m, pts, pose, 1, NDTPSO_SCORE_F64, &c), "cost_function"))  // builds if need be
+    const DeviceScan scan(new_frame, is_foreign, foreign, "cost_function");
+    if (ndtpso_host::check(ndtpso_map_cost(m, scan.pts, pose, 1, NDTPSO_SCORE_F64, &c), "cost_function"))  // builds if need be
       built = true;
     else
       c = 0.;
-    if (tmp) ndtpso_host::release_scan(tmp, tmp_cap);
     return c;
   }
   if (!built) build();
@@ -588,10 +586,13 @@ bool align_uses_frame_config() {
 }
 }  // namespace
 
-Vector3d NDTFrame::align(Vector3d initial_guess, const NDTFrame* const new_frame) {
-  Vector3d deviation = s_iter < 2 ? Vector3d(.1, .1, 3.1415E-3) : Vector3d((s_pose_diff * 2.).array().abs());
+Vector3d NDTFrame::nextDeviation() {
+  const Vector3d deviation = s_iter < 2 ? Vector3d(.1, .1, 3.1415E-3) : Vector3d((s_pose_diff * 2.).array().abs());
   ++s_iter;
-  Vector3d pose = optimize(initial_guess, new_frame, deviation, align_uses_frame_config() ? s_config.psoConfig : PSOConfig());
+  return deviation;
+}
+
+Vector3d NDTFrame::recordAlignedPose(Vector3d pose) {
 #if TRANSFORM_POSE_AFTER_ALIGN
   pose -= s_trans;
 #endif
@@ -600,10 +601,13 @@ Vector3d NDTFrame::align(Vector3d initial_guess, const NDTFrame* const new_frame
   return pose;
 }
 
-// Several align() calls, the device work of independent ones in one launch (see ndtframe.h).  Everything a sequence of align()
-// calls does on the host is done here in the same order: deviation and ++s_iter per frame (align), the map and the rand() draws
-// per request (optimize), then ONE ndtpso_map_align_batch for the run, then `built`, lastAlignOk(), the thread's failure flag
-// and s_pose_diff / s_prev_pose per request, again in order.
+Vector3d NDTFrame::align(Vector3d initial_guess, const NDTFrame* const new_frame) {
+  const Vector3d deviation = nextDeviation();
+  return recordAlignedPose(optimize(initial_guess, new_frame, deviation, align_uses_frame_config() ? s_config.psoConfig : PSOConfig()));
+}
+
+// Several align() calls, the device work of independent ones in one launch (see ndtframe.h): align()'s own steps in request
+// order, with ONE ndtpso_map_align_batch for a run of requests between the steps before the alignment and those after it.
 void NDTFrame::alignBatch(NDTAlignRequest* reqs, size_t n) {
   if (!reqs) return;
   ndtpso_host::Ctx* const mine = ndtpso_host::thread_ctx();
@@ -644,8 +648,7 @@ void NDTFrame::alignBatch(NDTAlignRequest* reqs, size_t n) {
     for (size_t k = 0; k < cnt; ++k) {
       NDTAlignRequest& r = reqs[i + k];
       NDTFrame* f = r.ref;
-      const Vector3d deviation = f->s_iter < 2 ? Vector3d(.1, .1, 3.1415E-3) : Vector3d((f->s_pose_diff * 2.).array().abs());
-      ++f->s_iter;
+      const Vector3d deviation = f->nextDeviation();
       ndtpso_map_align_job& job = jobs[k];
       job.map = f->ensureMap();
       no_map = no_map || !job.map;
@@ -675,16 +678,8 @@ void NDTFrame::alignBatch(NDTAlignRequest* reqs, size_t n) {
       // (a call refused as a whole -- no device context, a HIP error before the launch -- failed every request)
       const int rc = (rc_call != NDTPSO_OK && !some_job_failed) ? rc_call : jobs[k].rc;
       const bool ok = ndtpso_host::check(rc, "align");
-      if (ok) f->built = true;
-      f->s_last_align_ok = ok;
-      t_last_align_failed = !ok;
-      Vector3d pose = ok ? Vector3d(jobs[k].pose[0], jobs[k].pose[1], jobs[k].pose[2]) : r.guess;
-#if TRANSFORM_POSE_AFTER_ALIGN
-      pose -= f->s_trans;
-#endif
-      f->s_pose_diff = pose - f->s_prev_pose;
-      f->s_prev_pose = pose;
-      r.pose = pose;
+      f->recordAlignOutcome(ok);
+      r.pose = f->recordAlignedPose(ok ? Vector3d(jobs[k].pose[0], jobs[k].pose[1], jobs[k].pose[2]) : r.guess);
       r.ok = ok;
     }
     i = j;

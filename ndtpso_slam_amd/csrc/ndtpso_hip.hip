@@ -1716,8 +1716,97 @@ int ndtpso_process_counters(uint64_t* out, int n) {
   return NDTPSO_OK;
 }
 
+// Whether `n` alignments about to be launched from this context may run on clusters, and their count among the process's
+// alignments in flight until release() or the end of the scope.
+// A cluster's workgroups wait for each other, which is safe only while every cluster in flight is resident: alignments launched
+// from more host threads than the device has hardware queues to run side by side (16; a process's streams share them, and
+// streams on one queue take turns) are the case in which some cluster's workgroups sit behind another stream's kernel while
+// their siblings spin towards the exchange's bounded wait.  Past that many alignments in flight in the process, the next ones
+// run on ONE workgroup each: half as fast, and they wait for nobody.  (NDTPSO_CLUSTER_MAX_INFLIGHT, default 16.)
+struct ClusterAdmission {
+  bool allow;
+  ClusterAdmission(ndtpso_ctx* c, int n_aligns, bool allow_in = true) : allow(allow_in), n(n_aligns) {
+    static const int max_in_flight = [] {
+      const char* e = std::getenv("NDTPSO_CLUSTER_MAX_INFLIGHT");
+      return e ? std::max(0, std::atoi(e)) : 16;
+    }();
+    if (allow && c->cluster_penalty > 0) {  // (after a timeout: note_cluster_timeout)
+      --c->cluster_penalty;
+      allow = false;
+    }
+    const int before = g_aligns_in_flight.fetch_add(n, std::memory_order_relaxed);
+    if (allow && before + n > max_in_flight) {
+      allow = false;
+      g_crowded_aligns.fetch_add((unsigned long long)n, std::memory_order_relaxed);
+    }
+  }
+  void release() {
+    if (n) g_aligns_in_flight.fetch_sub(n, std::memory_order_relaxed);
+    n = 0;
+  }
+  ~ClusterAdmission() { release(); }
+  ClusterAdmission(const ClusterAdmission&) = delete;
+  ClusterAdmission& operator=(const ClusterAdmission&) = delete;
+
+ private:
+  int n;
+};
+
+// An alignment's cluster ran into the bounded wait (it was not co-resident: device shared with other work): counted, and no
+// new attempt from this context for the next 200 alignments (a robot's 5-20 s; one under the test hook).
+static void note_cluster_timeout(ndtpso_ctx* c) {
+  g_cluster_timeouts.fetch_add(1, std::memory_order_relaxed);
+  c->cluster_penalty = cluster_test_absent() >= 0 ? 1 : 200;
+}
+
+// How many workgroups share each of the `n_units` alignments of a launch, and their waves.  `share_device`: a cluster per
+// alignment only while the device has the compute units for all of them, and only one that pays for its exchanges.
+static void cluster_launch_k(const ndtpso_ctx* c, int P, uint32_t n_units, bool allow, bool share_device, int* K, int* cw) {
+  cluster_shape(P, true, allow, K, cw);
+  if (!share_device) return;
+  if (*K > 1) *K = std::min<int>(*K, c->n_cus / (int)std::min<uint32_t>(n_units, (uint32_t)c->n_cus));
+  if (*K < 2 || !cluster_worthwhile(*K, *cw)) *K = 1;
+}
+
+// The rest of a launch's shape once K and the LDS plan are known (launch_pairs' plan depends on K): the ClusterP, and for
+// K > 1 the items per round in `ps`, the speculation scratch behind `lds_total` (null: the caller's jobs have a layout each
+// and make that room themselves) and `unit_slots`, the uint4 exchange slots one alignment needs -- the caller provides
+// n_units * unit_slots of them as cl->xc.  `xcd`: the XCD of cluster 0.
+static void cluster_launch_shape(ndtpso_ctx* c, int P, int K, int waves, uint32_t n_units, int xcd, const uint32_t* redo_list,
+                                 uint32_t redo_mask, int* lds_total, PsoP* ps, ClusterP* cl, size_t* unit_slots) {
+  *cl = ClusterP{K, 0, 0, cluster_test_absent(), nullptr, 0u, cluster_one_xcd() ? 1 + xcd : 0, (int)n_units, -1,
+                 reinterpret_cast<double*>(const_cast<uint32_t*>(redo_list)) /* ClusterP::spec, on the host's side */,
+                 cluster_flags() | (int)(redo_mask << kClusterRedoShift)};
+  // (one XCD holds an eighth of the compute units: one XCD per cluster only while an XCD's share of the clusters finds a compute
+  // unit per workgroup there; a forced K, a partitioned part, a batch that fills the device are spread as the dispatcher
+  // spreads them instead of spinning to the exchange's timeout)
+  if (((int)n_units + 7) / 8 * K > std::max(1, c->n_cus / 8)) cl->one_xcd = 0;
+  *unit_slots = 0;
+  if (K < 2) return;
+  if (lds_total) cluster_spec_room(P, lds_total, cl);
+  ps->G = std::min(std::max(P, 1), K * waves);  // one item per wave and round
+  cl->stride = round_up(P + 1, 8);
+  // two exchange buffers of `stride` slots and one slot per rank, padded to eight: the kernels address them by the same rule
+  // (k_align_jobs in ndtpso_align_jobs.hip, k_align_pairs in ndtpso_pairs_body.inc)
+  *unit_slots = 2 * (size_t)cl->stride + (size_t)round_up(K, 8);
+  cl->nonce = next_cluster_nonce(c);
+}
+
+// A result slot -- [pose, cost | AlignStats] in doubles -- taken apart; a null destination is left out.
+constexpr size_t kResultDoubles = 4 + sizeof(AlignStats) / 8;
+static AlignStats result_of(const double* slot, double pose[3] = nullptr, double* cost = nullptr, ndtpso_align_stats* stats = nullptr) {
+  AlignStats st;
+  std::memcpy(&st, slot + 4, sizeof(st));
+  if (pose) std::memcpy(pose, slot, 3 * sizeof(double));
+  if (cost) *cost = slot[3];
+  if (stats) std::memcpy(stats, slot + 4, sizeof(AlignStats));
+  return st;
+}
+// the alignment of a shared or late-bound launch must be redone alone: with the fp64 score, behind the header, on one workgroup
+static bool must_redo_alone(const AlignStats& st) { return (st.status & (kStatusNeedsF64 | kStatusLateOverflow | kStatusClusterTimeout)) != 0; }
+
 static int align_once(ndtpso_ctx* c, const AlignSrc& src, const ndtpso_pso_config* cfg, uint32_t seed, bool have_table,
-                      int mode, double host[4 + sizeof(AlignStats) / 8], bool allow_cluster = true,
+                      int mode, double host[kResultDoubles], bool allow_cluster = true,
                       AfterLaunch after = AfterLaunch{nullptr, nullptr}) {
   Plan plan;
   const uint32_t n = src.n;
@@ -1744,29 +1833,9 @@ static int align_once(ndtpso_ctx* c, const AlignSrc& src, const ndtpso_pso_confi
     HIP_TRY(c, hipEventCreateWithFlags(&c->result_event, hipEventDisableTiming));
   }
   int K, cw;
-  if (allow_cluster && c->cluster_penalty > 0) {
-    --c->cluster_penalty;
-    allow_cluster = false;
-  }
-  // A cluster's workgroups wait for each other, which is safe only while every cluster in flight is resident: alignments launched
-  // from more host threads than the device has hardware queues to run side by side (16; a process's streams share them, and
-  // streams on one queue take turns) are the case in which some cluster's workgroups sit behind another stream's kernel while
-  // their siblings spin towards the exchange's bounded wait.  Past that many alignments in flight in the process, the next one
-  // runs on ONE workgroup: half as fast, and it waits for nobody.  (NDTPSO_CLUSTER_MAX_INFLIGHT, default 16.)
-  static const int max_clusters_in_flight = [] {
-    const char* e = std::getenv("NDTPSO_CLUSTER_MAX_INFLIGHT");
-    return e ? std::max(0, std::atoi(e)) : 16;
-  }();
-  struct InFlight {
-    InFlight() : before(g_aligns_in_flight.fetch_add(1, std::memory_order_relaxed)) {}
-    ~InFlight() { g_aligns_in_flight.fetch_sub(1, std::memory_order_relaxed); }
-    int before;
-  } in_flight;
-  if (allow_cluster && in_flight.before >= max_clusters_in_flight) {
-    allow_cluster = false;
-    g_crowded_aligns.fetch_add(1, std::memory_order_relaxed);
-  }
-  cluster_shape(cfg->population, true, allow_cluster, &K, &cw);
+  const ClusterAdmission admitted(c, 1, allow_cluster);
+  // (a lone alignment has the device to itself: no cap by compute units, and a cluster of any size is taken)
+  cluster_launch_k(c, cfg->population, 1, admitted.allow, false, &K, &cw);
   const unsigned long long seq = ++c->align_issued;
   const bool staged_table = have_table && c->inputs_pinned;
   const int table_vec = (int)((ndtpso_rand_draws(cfg) * 4 + 15) / 16);
@@ -1774,18 +1843,13 @@ static int align_once(ndtpso_ctx* c, const AlignSrc& src, const ndtpso_pso_confi
   if (L.swarm_global) HIP_TRY(c, c->ws.reserve((size_t)swarm_bytes(cfg->population, true, true) * (size_t)K));
   const int waves = K > 1 ? cw : pick_waves(cfg->population, L.total, 1);
   PsoP ps = make_pso(cfg, waves, mode, L.swarm_global != 0);
-  ClusterP cl{K, 0, 0, cluster_test_absent(), nullptr, 0u, cluster_one_xcd() ? 1 + c->xcd_pref : 0, 1, -1, nullptr, cluster_flags()};
+  ClusterP cl;
   int lds_total = L.total;
-  // (one XCD holds an eighth of the compute units; a cluster it cannot hold -- a forced K, a partitioned part -- is spread as
-  // the dispatcher spreads it instead of spinning to the exchange's timeout, as launch_pairs does)
-  if (K > std::max(1, c->n_cus / 8)) cl.one_xcd = 0;
-  if (K > 1) {
-    cluster_spec_room(cfg->population, &lds_total, &cl);
-    ps.G = std::min(std::max(cfg->population, 1), K * waves);  // one item per wave and round
-    cl.stride = round_up(cfg->population + 1, 8);
-    if (int rc = cluster_slots(c, ((size_t)2 * cl.stride + (size_t)round_up(K, 8)) * sizeof(uint4), &cl.xc)) return rc;
-    cl.nonce = next_cluster_nonce(c);
-  }
+  size_t unit_slots = 0;
+  // (the context's own XCD for its lone cluster: contexts of one process spread over the eight)
+  cluster_launch_shape(c, cfg->population, K, waves, 1, c->xcd_pref, nullptr, 0, &lds_total, &ps, &cl, &unit_slots);
+  if (K > 1)
+    if (int rc = cluster_slots(c, unit_slots * sizeof(uint4), &cl.xc)) return rc;
 #define LAUNCH_ALIGN_CA(MODE, PATH, CL, ARB)                                                                       \
   do {                                                                                                             \
   t_last_launch = launch_code(MODE == kScoreF64, PATH, CL, ARB, false, 0, false, false);                           \
@@ -1829,7 +1893,6 @@ static int align_once(ndtpso_ctx* c, const AlignSrc& src, const ndtpso_pso_confi
   // `after` enqueues (the occupancy grid a committed speculative build still owes) runs in the shadow of the host's
   // wake-up.  (With a pageable destination the copy call itself blocked until the kernel was done, `after` was
   // enqueued late and then waited for: 30 us per scan on the live path.)
-  constexpr size_t kResultBytes = (4 + sizeof(AlignStats) / 8) * sizeof(double);
   if (after.fn)
     if (int rc = after.fn(after.arg)) return rc;
   static const bool host_clock = std::getenv("NDTPSO_HOST_CLOCK") != nullptr;
@@ -1847,22 +1910,15 @@ static int align_once(ndtpso_ctx* c, const AlignSrc& src, const ndtpso_pso_confi
     }
     c->clk_wake = now;
   }
-  std::memcpy(host, c->result_pinned, kResultBytes);
-  if (K > 1) {
-    AlignStats st;
-    std::memcpy(&st, host + 4, sizeof(st));
-    if (st.status & kStatusClusterTimeout) {  // the cluster was not co-resident (device shared with other work): one workgroup,
-      g_cluster_timeouts.fetch_add(1, std::memory_order_relaxed);
-      static bool logged = false;
-      if (!logged) {
-        logged = true;
-        std::fprintf(stderr, "ndtpso: a cluster of %d workgroups did not meet within 20 ms (device shared?); alignments run on one workgroup for a while\n", K);
-      }
-      c->cluster_penalty = cluster_test_absent() >= 0 ? 1 : 200;  // and no new attempt for the next 200 alignments (a
-                                                                   // robot's 5-20 s; one under the test hook)
+  std::memcpy(host, c->result_pinned, kResultDoubles * sizeof(double));
+  if (K > 1 && (result_of(host).status & kStatusClusterTimeout)) {  // the cluster was not co-resident: one workgroup
+    note_cluster_timeout(c);
+    static bool logged = false;
+    if (!logged) {
+      logged = true;
+      std::fprintf(stderr, "ndtpso: a cluster of %d workgroups did not meet within 20 ms (device shared?); alignments run on one workgroup for a while\n", K);
     }
-    if (st.status & kStatusClusterTimeout)
-      return align_once(c, src, cfg, seed, have_table, exact ? NDTPSO_SCORE_EXACT : mode, host, false);
+    return align_once(c, src, cfg, seed, have_table, exact ? NDTPSO_SCORE_EXACT : mode, host, false);
   }
   return NDTPSO_OK;
 }
@@ -1909,22 +1965,16 @@ static int align_points(ndtpso_ctx* c, const double* xy, uint32_t n, const doubl
 static int align_finish(ndtpso_ctx* c, const AlignSrc& src, const ndtpso_pso_config* cfg, uint32_t seed, bool have_table,
                         int mode, double out_pose[3], double* out_cost, ndtpso_align_stats* stats, AfterLaunch after,
                         bool allow_cluster) {
-  double host[4 + sizeof(AlignStats) / 8];
+  double host[kResultDoubles];
   int rc = align_once(c, src, cfg, seed, have_table, mode, host, allow_cluster, after);
   if (rc != NDTPSO_OK) return rc;
-  AlignStats st;
-  std::memcpy(&st, host + 4, sizeof(st));
-  if (mode != NDTPSO_SCORE_F64 && (st.status & kStatusNeedsF64)) {
+  if (mode != NDTPSO_SCORE_F64 && (result_of(host).status & kStatusNeedsF64)) {
     static const bool log_redo = std::getenv("NDTPSO_LOG_REDO") != nullptr;  // diagnostics: how often this happens
     if (log_redo) std::fprintf(stderr, "ndtpso: alignment handed to the fp64-score kernel\n");
     rc = align_once(c, src, cfg, seed, have_table, NDTPSO_SCORE_F64, host);
     if (rc != NDTPSO_OK) return rc;
   }
-  out_pose[0] = host[0];
-  out_pose[1] = host[1];
-  out_pose[2] = host[2];
-  if (out_cost) *out_cost = host[3];
-  if (stats) std::memcpy(stats, host + 4, sizeof(AlignStats));
+  result_of(host, out_pose, out_cost, stats);
   return NDTPSO_OK;
 }
 
@@ -1996,9 +2046,7 @@ static int launch_pairs(ndtpso_ctx* c, uint32_t n_pairs, const float* d_ref, con
   int K = 1, cw = 4;
   if (t_plan_force.cluster >= 0) allow_cluster = t_plan_force.cluster != 0;
   const uint32_t n_units = redo_list ? redo_units : n_pairs;  // alignments this launch provides for (scratch, exchange slots, grid)
-  cluster_shape(cfg->population, true, allow_cluster && gate == 0, &K, &cw);
-  if (K > 1) K = std::min<int>(K, c->n_cus / (int)std::min<uint32_t>(n_units, (uint32_t)c->n_cus));
-  if (K < 2 || !cluster_worthwhile(K, cw)) K = 1;
+  cluster_launch_k(c, cfg->population, n_units, allow_cluster && gate == 0, true, &K, &cw);
   if (redo_list && K < 2) return NDTPSO_E_STATE;  // (not an error of the call: the gated launches serve the pairs)
   GridP g;
   WinP wn;
@@ -2017,20 +2065,12 @@ static int launch_pairs(ndtpso_ctx* c, uint32_t n_pairs, const float* d_ref, con
   if (int rc = make_scan(c, geom, &sp, &dirs)) return rc;
   if (K > 1) waves = cw;
   PsoP ps = make_pso(cfg, waves, mode, plan.L.swarm_global != 0);
-  ClusterP cl{K, 0, 0, cluster_test_absent(), nullptr, 0u, cluster_one_xcd(), (int)n_units, -1,
-              reinterpret_cast<double*>(const_cast<uint32_t*>(redo_list)) /* ClusterP::spec, on the host's side */,
-              cluster_flags() | (int)(redo_mask << kClusterRedoShift)};
+  ClusterP cl;
   int lds_total = plan.L.total;
-  if (K > 1) cluster_spec_room(cfg->population, &lds_total, &cl);
-  // (one XCD per cluster only while an XCD's share of the clusters finds a compute unit per workgroup there; a batch that
-  // fills the device is spread as the dispatcher spreads it)
-  if (((int)n_units + 7) / 8 * K > std::max(1, c->n_cus / 8)) cl.one_xcd = 0;
-  if (K > 1) {
-    ps.G = std::min(std::max(cfg->population, 1), K * waves);
-    cl.stride = round_up(cfg->population + 1, 8);
-    if (int rc = cluster_slots(c, (size_t)n_units * (2 * cl.stride + round_up(K, 8)) * sizeof(uint4), &cl.xc)) return rc;
-    cl.nonce = next_cluster_nonce(c);
-  }
+  size_t unit_slots = 0;
+  cluster_launch_shape(c, cfg->population, K, waves, n_units, 0, redo_list, redo_mask, &lds_total, &ps, &cl, &unit_slots);
+  if (K > 1)
+    if (int rc = cluster_slots(c, (size_t)n_units * unit_slots * sizeof(uint4), &cl.xc)) return rc;
   const size_t stride = ndtpso_rand_draws(cfg);
   const size_t ws_stride = plan.L.swarm_global ? (size_t)swarm_bytes(cfg->population, true, true) : 0;
   if (ws_stride) HIP_TRY(c, c->ws.reserve(ws_stride * n_units * (size_t)K));

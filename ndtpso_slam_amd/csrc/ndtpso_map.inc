@@ -748,6 +748,60 @@ int map_settle(ndtpso_map* m) {
 
 int map_commit_speculation_cb(void* m) { return map_commit_speculation(static_cast<ndtpso_map*>(m)); }
 
+// the window of the table a header describes: what the LDS plan of an alignment or a cost goes by
+WinP window_of(const MapHeader& h) {
+  WinP wn;
+  wn.x0 = h.x0;
+  wn.y0 = h.y0;
+  wn.w = h.x1 - h.x0 + 1;
+  wn.h = h.y1 - h.y0 + 1;
+  wn.n_words = (int)h.n_words;
+  wn.rec_cap = std::max<int>((int)h.n_built, 1);
+  return wn;
+}
+
+// Late window binding: a speculative build's header is still on its way when the node asks for the alignment (the
+// pack kernel has not even run) -- instead of waiting for it, the layout is planned for an upper bound (the whole grid;
+// the built cells of the header this host saw last plus one per point inserted since) and the kernel takes the real
+// window from the device.  The host then enqueues the alignment straight behind the build, and the device goes from
+// one to the other without the 10-20 us of idle time the header's trip to the host and the launch cost.  Any doubt (no
+// earlier header, a plan that is not the dense form -- the caller probes that with `ub` --, the bound exceeded, an
+// alignment to be redone) ends in the synchronous path: map_await_header.
+bool map_late_bound(const ndtpso_map* m, int mode, WinP* ub) {
+  static const bool allow_late = [] {
+    const char* e = std::getenv("NDTPSO_LATE_WINDOW");  // tuning / test knob: =0 always waits for the header
+    return !(e && e[0] == '0');
+  }();
+  if (!m->spec || !allow_late || mode == NDTPSO_SCORE_F64 || m->known_pts == ~0ull || m->known_pts != m->spec_prev_pts ||
+      m->build_pts < m->known_pts)
+    return false;
+  const unsigned long long grown = (unsigned long long)m->host_hdr.n_built + (m->build_pts - m->known_pts);
+  ub->x0 = 0;
+  ub->y0 = 0;
+  ub->w = m->p.g.W;
+  ub->h = m->p.g.H;
+  ub->n_words = (ub->w * ub->h + 31) / 32;
+  ub->rec_cap = (int)std::min<unsigned long long>((unsigned long long)m->p.n_cells, std::max<unsigned long long>(grown, 1ull));
+  static const bool test_overflow = std::getenv("NDTPSO_LATE_TEST_OVERFLOW") != nullptr;  // test hook: a bound the table exceeds
+  if (test_overflow) ub->rec_cap = 1;
+  return true;
+}
+
+// the header of a speculative build whose pack kernel has run (it wrote it to pinned memory itself) becomes the host's
+int map_take_spec_header(ndtpso_map* m) {
+  m->host_hdr = *m->spec_hdr;
+  m->known_pts = m->build_pts;
+  if (m->host_hdr.status & kMapPoolExhausted) return fail(m->ctx, NDTPSO_E_CAPACITY, "map point pool exhausted");
+  return NDTPSO_OK;
+}
+
+// the header of the map's latest build with the host: a speculative build's is already on its way, any other is fetched
+int map_await_header(ndtpso_map* m) {
+  if (!m->spec) return map_fetch_header(m);
+  if (int rc = wait_pinned_word(m->ctx, reinterpret_cast<const uint32_t*>(m->spec_hdr) + kSpecSeqWord, m->spec_seq)) return rc;
+  return map_take_spec_header(m);
+}
+
 // NDTFrame::addPoint for every point (ndtframe.cpp:215-225): a point that lands in the frame clears `built`, one that
 // does not leaves it alone -- and that matters, because a build repeated on unchanged cells is not a no-op in floating
 // point (WINDOW_ADD, ndtcell.h:13-15: (global + partial) - partial).  `accepted`: 1 some point lands in the frame,
@@ -1130,8 +1184,7 @@ int ndtpso_map_align(ndtpso_map* m, const ndtpso_points* pts, const double guess
   if (int rc = exact_mode_resolve(c, &mode)) return rc;
   c->clk_enter = std::chrono::steady_clock::now();
   HIP_TRY(c, hipSetDevice(c->device));
-  const bool from_speculation = m->spec;
-  if (!from_speculation && !m->built) {  // cost_function's lazy build, core.cpp:27-28
+  if (!m->spec && !m->built) {  // cost_function's lazy build, core.cpp:27-28
     if (int rc = map_enqueue_build(m)) return rc;
   }
   const size_t n_draw = ndtpso_rand_draws(cfg);
@@ -1151,79 +1204,35 @@ int ndtpso_map_align(ndtpso_map* m, const ndtpso_points* pts, const double guess
     c->inputs = staged;
     c->inputs_pinned = true;
   }
-  // Late window binding: a speculative build's header is still on its way when the node asks for the alignment (the
-  // pack kernel has not even run) -- instead of waiting for it, the layout is planned for an upper bound (the whole grid;
-  // the built cells of the header this host saw last plus one per point inserted since) and the kernel takes the real
-  // window from the device.  The host then enqueues the alignment straight behind the build, and the device goes from
-  // one to the other without the 10-20 us of idle time the header's trip to the host and the launch cost.  Any doubt (no
-  // earlier header, a plan that is not the dense form, the bound exceeded, an alignment to be redone) ends in the
-  // synchronous path below.
-  static const bool allow_late = [] {
-    const char* e = std::getenv("NDTPSO_LATE_WINDOW");  // tuning / test knob: =0 always waits for the header
-    return !(e && e[0] == '0');
-  }();
+  // late window binding: planned for an upper bound, launched straight behind the speculative build (map_late_bound)
   bool late_done = false;  // the late path ran: speculation committed, header with the host
-  if (from_speculation && allow_late && m->known_pts != ~0ull && m->known_pts == m->spec_prev_pts && m->build_pts >= m->known_pts) {
-    const unsigned long long grown = (unsigned long long)m->host_hdr.n_built + (m->build_pts - m->known_pts);
-    WinP ub;
-    ub.x0 = 0;
-    ub.y0 = 0;
-    ub.w = m->p.g.W;
-    ub.h = m->p.g.H;
-    ub.n_words = (ub.w * ub.h + 31) / 32;
-    ub.rec_cap = (int)std::min<unsigned long long>((unsigned long long)m->p.n_cells, std::max<unsigned long long>(grown, 1ull));
-    static const bool test_overflow = std::getenv("NDTPSO_LATE_TEST_OVERFLOW") != nullptr;  // test hook: a bound the table exceeds
-    if (test_overflow) ub.rec_cap = 1;
-    AlignSrc late{(const unsigned char*)m->image.p, m->p.g, ub, (const double2*)pts->xy.p,
-                  std::max<uint32_t>(pts->n_upper, 1u), (const uint32_t*)pts->n_dev.p, out_cost != nullptr};
-    late.late_hdr = reinterpret_cast<const uint32_t*>(m->hdr.p);
-    Plan probe;
-    const bool exact_req = mode == NDTPSO_SCORE_EXACT;
-    if (mode != NDTPSO_SCORE_F64 &&
-        make_plan(NDTPSO_SCORE_F32, late.g, late.wn, (int)late.n, cfg->population, &probe, false, true, true, exact_req) && probe.path == 2) {
-      double host[4 + sizeof(AlignStats) / 8];
-      const AfterLaunch og{&map_commit_speculation_cb, m};
-      const int rc = align_once(c, late, cfg, seed, rand_table != nullptr, mode, host, true, og);
-      if (rc != NDTPSO_OK) return rc;
-      m->host_hdr = *m->spec_hdr;  // written by the pack kernel, which precedes the alignment on the stream
-      m->known_pts = m->build_pts;
-      if (m->host_hdr.status & kMapPoolExhausted) return fail(c, NDTPSO_E_CAPACITY, "map point pool exhausted");
-      AlignStats st;
-      std::memcpy(&st, host + 4, sizeof(st));
-      if (!(st.status & (kStatusNeedsF64 | kStatusLateOverflow | kStatusClusterTimeout))) {
-        out_pose[0] = host[0];
-        out_pose[1] = host[1];
-        out_pose[2] = host[2];
-        if (out_cost) *out_cost = host[3];
-        if (stats) std::memcpy(stats, host + 4, sizeof(AlignStats));
-        ++m->late_aligned;
-        return NDTPSO_OK;
-      }
-      late_done = true;
-      ++m->late_fallbacks;
-      if (st.status & kStatusNeedsF64) mode = NDTPSO_SCORE_F64;  // (what align_finish would do next)
+  AlignSrc src{(const unsigned char*)m->image.p, m->p.g, WinP{}, (const double2*)pts->xy.p,
+               std::max<uint32_t>(pts->n_upper, 1u), (const uint32_t*)pts->n_dev.p, out_cost != nullptr};
+  Plan probe;
+  if (map_late_bound(m, mode, &src.wn) &&
+      make_plan(NDTPSO_SCORE_F32, src.g, src.wn, (int)src.n, cfg->population, &probe, false, true, true, mode == NDTPSO_SCORE_EXACT) &&
+      probe.path == 2) {
+    src.late_hdr = reinterpret_cast<const uint32_t*>(m->hdr.p);
+    double host[kResultDoubles];
+    const AfterLaunch og{&map_commit_speculation_cb, m};
+    if (int rc = align_once(c, src, cfg, seed, rand_table != nullptr, mode, host, true, og)) return rc;
+    if (int rc = map_take_spec_header(m)) return rc;  // written by the pack kernel, which precedes the alignment on the stream
+    const AlignStats st = result_of(host);
+    if (!must_redo_alone(st)) {
+      result_of(host, out_pose, out_cost, stats);
+      ++m->late_aligned;
+      return NDTPSO_OK;
     }
+    late_done = true;
+    ++m->late_fallbacks;
+    if (st.status & kStatusNeedsF64) mode = NDTPSO_SCORE_F64;  // (what align_finish would do next)
+    src.late_hdr = nullptr;
   }
   // the table's window and size decide the LDS plan
-  const bool still_speculative = m->spec;
-  if (still_speculative) {  // built and packed ahead of time, its header already on its way to the host
-    if (int rc = wait_pinned_word(c, reinterpret_cast<const uint32_t*>(m->spec_hdr) + kSpecSeqWord, m->spec_seq)) return rc;
-    m->host_hdr = *m->spec_hdr;
-    m->known_pts = m->build_pts;
-    if (m->host_hdr.status & kMapPoolExhausted) return fail(c, NDTPSO_E_CAPACITY, "map point pool exhausted");
-  } else if (!late_done) {
-    if (int rc = map_fetch_header(m)) return rc;
-  }
-  const MapHeader& h = m->host_hdr;
-  WinP wn;
-  wn.x0 = h.x0;
-  wn.y0 = h.y0;
-  wn.w = h.x1 - h.x0 + 1;
-  wn.h = h.y1 - h.y0 + 1;
-  wn.n_words = (int)h.n_words;
-  wn.rec_cap = std::max<int>((int)h.n_built, 1);
-  const AlignSrc src{(const unsigned char*)m->image.p, m->p.g, wn, (const double2*)pts->xy.p,
-                     std::max<uint32_t>(pts->n_upper, 1u), (const uint32_t*)pts->n_dev.p, out_cost != nullptr};
+  const bool still_speculative = m->spec;  // built and packed ahead of time, its header already on its way to the host
+  if (still_speculative || !late_done)
+    if (int rc = map_await_header(m)) return rc;
+  src.wn = window_of(m->host_hdr);
   // the occupancy grid a committed speculation still owes is not read by the alignment: it follows it
   const AfterLaunch og{still_speculative ? &map_commit_speculation_cb : nullptr, m};
   return align_finish(c, src, cfg, seed, rand_table != nullptr, mode, out_pose, out_cost, stats, og);
@@ -1253,16 +1262,8 @@ int ndtpso_map_cost(ndtpso_map* m, ndtpso_points* pts, const double* poses, uint
   uint32_t n = 0;
   HIP_TRY(c, hipMemcpy(&n, pts->n_dev.p, 4, hipMemcpyDeviceToHost));
   pts->n_upper = n;
-  const MapHeader& h = m->host_hdr;
-  WinP wn;
-  wn.x0 = h.x0;
-  wn.y0 = h.y0;
-  wn.w = h.x1 - h.x0 + 1;
-  wn.h = h.y1 - h.y0 + 1;
-  wn.n_words = (int)h.n_words;
-  wn.rec_cap = std::max<int>((int)h.n_built, 1);
-  return cost_launch(c, (const unsigned char*)m->image.p, m->p.g, wn, (const double2*)pts->xy.p, n, poses, n_poses, mode,
-                     costs, nullptr);
+  return cost_launch(c, (const unsigned char*)m->image.p, m->p.g, window_of(m->host_hdr), (const double2*)pts->xy.p, n, poses, n_poses,
+                     mode, costs, nullptr);
 }
 
 // ---- exports (shutdown / inspection; synchronous, the host walks the downloaded structures) -----------------------

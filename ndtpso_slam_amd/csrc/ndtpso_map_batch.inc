@@ -3,13 +3,13 @@
 
 namespace {
 
-constexpr size_t kJobSlotBytes = 128;  // a job's pinned result slot: [pose, cost | AlignStats | the job's number], as the single path's
+constexpr size_t kJobSlotBytes = 128;  // a job's pinned result slot: [pose, cost | AlignStats | the job's number] (result_of)
 constexpr uint32_t kLaunchJobForm = 1u << 13;  // t_last_launch: the instantiation was k_align_jobs' (launch_code's other bits as k_align's)
 
 struct BatchMap {  // a distinct map of a call
   ndtpso_map* m;
   int rc;             // of its preparation: every job on it inherits a failure
-  bool late;          // launched behind a speculative build whose header the host has not seen (ndtpso_map_align's late path)
+  bool late;          // launched behind a speculative build whose header the host has not seen (map_late_bound)
   bool batched;       // at least one of its jobs is in a launch
   WinP wn;            // the window its jobs are planned with: the header's, or the late path's upper bound
 };
@@ -30,25 +30,6 @@ struct BatchGroup {   // the jobs of one launch: one kernel instantiation
   size_t first;       // its first job's place among the call's batched jobs (descriptors, result slots, scratch)
   size_t xc_off;      // its exchange slots within c->cluster_xc, in uint4
 };
-
-static bool batch_allow_late() {
-  static const bool allow = [] {
-    const char* e = std::getenv("NDTPSO_LATE_WINDOW");  // =0 always waits for the header (ndtpso_map_align)
-    return !(e && e[0] == '0');
-  }();
-  return allow;
-}
-static bool batch_test_overflow() {
-  static const bool t = std::getenv("NDTPSO_LATE_TEST_OVERFLOW") != nullptr;  // test hook: a bound the table exceeds (ndtpso_map_align)
-  return t;
-}
-static int batch_max_in_flight() {
-  static const int n = [] {
-    const char* e = std::getenv("NDTPSO_CLUSTER_MAX_INFLIGHT");  // (align_once)
-    return e ? std::max(0, std::atoi(e)) : 16;
-  }();
-  return n;
-}
 
 // which job kernel, if any, runs an alignment of `mode` against a table of window `wn`: -1 none (the single path)
 static int batch_plan_job(int mode, const GridP& g, const WinP& wn, uint32_t n, const ndtpso_pso_config* cfg, Plan* plan) {
@@ -102,7 +83,7 @@ extern "C" int ndtpso_map_align_batch(ndtpso_ctx* c, ndtpso_map_align_job* jobs,
   if (int rc = exact_jobs_resolve(c, asked, &mode)) return rc;
   HIP_TRY(c, hipSetDevice(c->device));
 
-  // ---- every distinct map once, as ndtpso_map_align prepares it --------------------------------------------------------
+  // ---- every distinct map once -----------------------------------------------------------------------------------------
   std::vector<BatchMap> maps;
   std::vector<BatchJob> bj(n_jobs);
   for (uint32_t i = 0; i < n_jobs; ++i) {
@@ -125,18 +106,9 @@ extern "C" int ndtpso_map_align_batch(ndtpso_ctx* c, ndtpso_map_align_job* jobs,
     if (!m->spec && !m->built) {  // cost_function's lazy build, core.cpp:27-28
       if ((bm.rc = map_enqueue_build(m)) != NDTPSO_OK) continue;
     }
-    // late window binding, under ndtpso_map_align's conditions -- and only if every job on the map has a dense-form job kernel
-    if (m->spec && batch_allow_late() && mode != NDTPSO_SCORE_F64 && m->known_pts != ~0ull && m->known_pts == m->spec_prev_pts &&
-        m->build_pts >= m->known_pts) {
-      const unsigned long long grown = (unsigned long long)m->host_hdr.n_built + (m->build_pts - m->known_pts);
-      WinP ub;
-      ub.x0 = 0;
-      ub.y0 = 0;
-      ub.w = m->p.g.W;
-      ub.h = m->p.g.H;
-      ub.n_words = (ub.w * ub.h + 31) / 32;
-      ub.rec_cap = (int)std::min<unsigned long long>((unsigned long long)m->p.n_cells, std::max<unsigned long long>(grown, 1ull));
-      if (batch_test_overflow()) ub.rec_cap = 1;
+    // late window binding, only if every job on the map has a dense-form job kernel
+    WinP ub;
+    if (map_late_bound(m, mode, &ub)) {
       bool all_dense = true;
       for (uint32_t i = 0; i < n_jobs && all_dense; ++i) {
         if (bj[i].map != (int)k) continue;
@@ -150,24 +122,8 @@ extern "C" int ndtpso_map_align_batch(ndtpso_ctx* c, ndtpso_map_align_job* jobs,
         continue;
       }
     }
-    if (m->spec) {  // built and packed ahead of time, its header already on its way to the host
-      if ((bm.rc = wait_pinned_word(c, reinterpret_cast<const uint32_t*>(m->spec_hdr) + kSpecSeqWord, m->spec_seq)) != NDTPSO_OK) continue;
-      m->host_hdr = *m->spec_hdr;
-      m->known_pts = m->build_pts;
-      if (m->host_hdr.status & kMapPoolExhausted) {
-        bm.rc = fail(c, NDTPSO_E_CAPACITY, "map point pool exhausted");
-        continue;
-      }
-    } else if ((bm.rc = map_fetch_header(m)) != NDTPSO_OK) {
-      continue;
-    }
-    const MapHeader& h = m->host_hdr;
-    bm.wn.x0 = h.x0;
-    bm.wn.y0 = h.y0;
-    bm.wn.w = h.x1 - h.x0 + 1;
-    bm.wn.h = h.y1 - h.y0 + 1;
-    bm.wn.n_words = (int)h.n_words;
-    bm.wn.rec_cap = std::max<int>((int)h.n_built, 1);
+    if ((bm.rc = map_await_header(m)) != NDTPSO_OK) continue;
+    bm.wn = window_of(m->host_hdr);
   }
 
   // ---- which jobs share a launch ---------------------------------------------------------------------------------------
@@ -200,12 +156,6 @@ extern "C" int ndtpso_map_align_batch(ndtpso_ctx* c, ndtpso_map_align_job* jobs,
     n_batched = 0;
   }
 
-  struct InFlight {  // the launches' alignments count as the single path's do (align_once)
-    int n = 0;
-    ~InFlight() {
-      if (n) g_aligns_in_flight.fetch_sub(n, std::memory_order_relaxed);
-    }
-  } in_flight;
   int first_rc = NDTPSO_OK;
   // A failure of the call itself once the batch is being put together: no job has a result yet, so every job that has not failed
   // on its own carries the call's code (a C caller reads per-job rc), and what was launched is waited for -- the kernels read the
@@ -224,17 +174,8 @@ extern "C" int ndtpso_map_align_batch(ndtpso_ctx* c, ndtpso_map_align_job* jobs,
   } while (0)
   if (n_batched) {
     c->clk_enter = std::chrono::steady_clock::now();
-    const int before = g_aligns_in_flight.fetch_add((int)n_batched, std::memory_order_relaxed);
-    in_flight.n = (int)n_batched;
-    bool allow_cluster = true;
-    if (c->cluster_penalty > 0) {
-      --c->cluster_penalty;
-      allow_cluster = false;
-    }
-    if (allow_cluster && before + (int)n_batched > batch_max_in_flight()) {
-      allow_cluster = false;
-      g_crowded_aligns.fetch_add(n_batched, std::memory_order_relaxed);
-    }
+    ClusterAdmission admitted(c, (int)n_batched);
+    bool allow_cluster = admitted.allow;
     if (t_plan_force.cluster >= 0) allow_cluster = t_plan_force.cluster != 0;  // (the check of the job kernels runs both forms)
     const int P = cfg->population;
     const size_t n_draw = ndtpso_rand_draws(cfg);
@@ -242,31 +183,23 @@ extern "C" int ndtpso_map_align_batch(ndtpso_ctx* c, ndtpso_map_align_job* jobs,
     size_t first = 0, xc_total = 0, copies = 0, staged_bytes = round_up((int)(n_batched * sizeof(AlignJob)), 256);
     for (BatchGroup& gr : groups) {
       const uint32_t n = (uint32_t)gr.jobs.size();
-      // launch_pairs' rules: a cluster per job while the device has the compute units, and only one that pays for its exchanges
-      cluster_shape(P, true, allow_cluster, &gr.K, &gr.cw);
-      if (gr.K > 1) gr.K = std::min<int>(gr.K, c->n_cus / (int)std::min<uint32_t>(n, (uint32_t)c->n_cus));
-      if (gr.K < 2 || !cluster_worthwhile(gr.K, gr.cw)) gr.K = 1;
+      cluster_launch_k(c, P, n, allow_cluster, true, &gr.K, &gr.cw);
       gr.lds_total = 0;
-      gr.cl = ClusterP{gr.K, 0, 0, cluster_test_absent(), nullptr, 0u, cluster_one_xcd(), (int)n, -1, nullptr, cluster_flags()};
-      for (uint32_t i : gr.jobs) {
+      for (uint32_t i : gr.jobs) {  // (every job has a layout of its own, and its speculation scratch behind it)
         int lds = bj[i].plan.L.total;
-        ClusterP room = gr.cl;
+        ClusterP room;
+        room.spec_off = -1;
         if (gr.K > 1) cluster_spec_room(P, &lds, &room);
         bj[i].spec_off = room.spec_off;
         gr.lds_total = std::max(gr.lds_total, lds);  // the launch's dynamic LDS is its largest job's
       }
       gr.waves = gr.K > 1 ? gr.cw : pick_waves(P, gr.lds_total, 1);
       gr.ps = make_pso(cfg, gr.waves, gr.kind == 2 ? NDTPSO_SCORE_F64 : NDTPSO_SCORE_F32, false);
-      // (one XCD per cluster only while an XCD's share of the clusters finds a compute unit per workgroup there)
-      if (((int)n + 7) / 8 * gr.K > std::max(1, c->n_cus / 8)) gr.cl.one_xcd = 0;
+      size_t unit_slots = 0;  // (no lds_total: the speculation scratch was placed per job above, AlignJob::spec_off)
+      cluster_launch_shape(c, P, gr.K, gr.waves, n, 0, nullptr, 0, nullptr, &gr.ps, &gr.cl, &unit_slots);
       gr.first = first;
       gr.xc_off = xc_total;
-      if (gr.K > 1) {
-        gr.ps.G = std::min(std::max(P, 1), gr.K * gr.waves);  // one item per wave and round
-        gr.cl.stride = round_up(P + 1, 8);
-        xc_total += (size_t)n * (2 * (size_t)gr.cl.stride + (size_t)round_up(gr.K, 8));
-        gr.cl.nonce = next_cluster_nonce(c);
-      }
+      xc_total += (size_t)n * unit_slots;
       for (uint32_t i : gr.jobs) {
         if (jobs[i].rand_table) {
           copies += (size_t)gr.K;
@@ -358,46 +291,31 @@ extern "C" int ndtpso_map_align_batch(ndtpso_ctx* c, ndtpso_map_align_job* jobs,
       }
     }
     c->align_seen = c->align_issued;
-    g_aligns_in_flight.fetch_sub(in_flight.n, std::memory_order_relaxed);
-    in_flight.n = 0;
+    admitted.release();
     // the headers the late launches ran ahead of: written by the pack kernels, which precede the alignments on the stream
-    for (BatchMap& bm : maps) {
-      if (!bm.late) continue;
-      ndtpso_map* m = bm.m;
-      m->host_hdr = *m->spec_hdr;
-      m->known_pts = m->build_pts;
-      if (m->host_hdr.status & kMapPoolExhausted) bm.rc = fail(c, NDTPSO_E_CAPACITY, "map point pool exhausted");
-    }
+    for (BatchMap& bm : maps)
+      if (bm.late) bm.rc = map_take_spec_header(bm.m);
     for (const BatchGroup& gr : groups) {
       size_t at = gr.first;
       for (uint32_t i : gr.jobs) {
         ndtpso_map_align_job& j = jobs[i];
         BatchMap& bm = maps[(size_t)bj[i].map];
-        double host[4 + sizeof(AlignStats) / 8];
+        double host[kResultDoubles];
         std::memcpy(host, static_cast<const unsigned char*>(c->jobs_pinned) + at * kJobSlotBytes, sizeof(host));
         ++at;
         if (bm.rc != NDTPSO_OK) {
           j.rc = bm.rc;
           continue;
         }
-        AlignStats st;
-        std::memcpy(&st, host + 4, sizeof(st));
-        if (st.status & (kStatusNeedsF64 | kStatusLateOverflow | kStatusClusterTimeout)) {
-          // redone alone, by the single path's rules: the fp64 score after the underflow flag, no cluster after a timeout
+        const AlignStats st = result_of(host);
+        if (must_redo_alone(st)) {  // the fp64 score after the underflow flag, no cluster after a timeout
           if (bm.late) ++bm.m->late_fallbacks;
-          if (st.status & kStatusClusterTimeout) {  // (counted per alignment, as the single path counts them)
-            g_cluster_timeouts.fetch_add(1, std::memory_order_relaxed);
-            c->cluster_penalty = cluster_test_absent() >= 0 ? 1 : 200;
-          }
+          if (st.status & kStatusClusterTimeout) note_cluster_timeout(c);
           bj[i].kind = (st.status & kStatusNeedsF64) ? -2 : -1;
           continue;
         }
         if (bm.late) ++bm.m->late_aligned;
-        j.pose[0] = host[0];
-        j.pose[1] = host[1];
-        j.pose[2] = host[2];
-        if (j.flags & 1u) j.cost = host[3];
-        std::memcpy(&j.stats, host + 4, sizeof(AlignStats));
+        result_of(host, j.pose, (j.flags & 1u) ? &j.cost : nullptr, &j.stats);
         j.route = gr.K;
       }
     }

@@ -41,7 +41,8 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 LLVM = "/opt/rocm/lib/llvm/bin"
 
 
-def extract_code_object(lib: str) -> bytes:
+def extract_code_objects(lib: str) -> list[bytes]:
+    """The gfx950 code object of every translation unit of the library (one offload bundle each, in link order)."""
     out = subprocess.check_output([os.path.join(LLVM, "llvm-readelf"), "-S", "-W", lib], text=True)
     m = re.search(r"\.hip_fatbin\s+\S+\s+([0-9a-f]+)\s+([0-9a-f]+)\s+([0-9a-f]+)", out)
     if not m:
@@ -49,19 +50,32 @@ def extract_code_object(lib: str) -> bytes:
     off, size = int(m.group(2), 16), int(m.group(3), 16)
     with open(lib, "rb") as f:
         f.seek(off)
-        data = f.read(size)
-    if data[:24] != b"__CLANG_OFFLOAD_BUNDLE__":
+        section = f.read(size)
+    magic = b"__CLANG_OFFLOAD_BUNDLE__"
+    if section[:24] != magic:
         raise SystemExit("unexpected fat binary format (compressed bundle?)")
-    n = struct.unpack_from("<Q", data, 24)[0]
-    p = 32
-    for _ in range(n):
-        o, s, t = struct.unpack_from("<QQQ", data, p)
-        p += 24
-        triple = data[p:p + t].decode()
-        p += t
-        if "gfx950" in triple and s:
-            return data[o:o + s]
-    raise SystemExit("no gfx950 code object in the bundle")
+    found = []
+    at = 0
+    while at >= 0:
+        nxt = section.find(magic, at + 24)
+        data = section[at:nxt if nxt >= 0 else len(section)]
+        n = struct.unpack_from("<Q", data, 24)[0]
+        p = 32
+        for _ in range(n):
+            o, s, t = struct.unpack_from("<QQQ", data, p)
+            p += 24
+            triple = data[p:p + t].decode()
+            p += t
+            if "gfx950" in triple and s:
+                found.append(data[o:o + s])
+        at = nxt
+    if not found:
+        raise SystemExit("no gfx950 code object in the bundle")
+    return found
+
+
+def extract_code_object(lib: str) -> bytes:
+    return extract_code_objects(lib)[0]  # ndtpso_hip.hip's: the kernels but the job kernels
 
 
 def disassemble(code: bytes) -> list[str]:

@@ -18,8 +18,16 @@ import isa_mix  # noqa: E402
 
 
 def kernel_text(lib, want):
+    for code in isa_mix.extract_code_objects(lib):  # (one per translation unit: the job kernels have their own)
+        text = code_object_kernel_text(code, want)
+        if text is not None:
+            return text
+    raise SystemExit("%s: no kernel matching %r" % (lib, want))
+
+
+def code_object_kernel_text(code, want):
     with tempfile.NamedTemporaryFile(suffix=".co") as f:
-        f.write(isa_mix.extract_code_object(lib))
+        f.write(code)
         f.flush()
         nm = subprocess.check_output([os.path.join(isa_mix.LLVM, "llvm-readelf"), "--symbols", "--wide", f.name], text=True)
         syms = [l.split()[-1] for l in nm.splitlines() if " FUNC " in l]
@@ -30,7 +38,7 @@ def kernel_text(lib, want):
                 hit = sname
                 break
         if not hit:
-            raise SystemExit("%s: no kernel matching %r" % (lib, want))
+            return None
         txt = subprocess.check_output([os.path.join(isa_mix.LLVM, "llvm-objdump"), "-d", "--no-show-raw-insn", "--no-leading-addr",
                                        "--disassemble-symbols=" + hit, f.name], text=True)
     out = []
