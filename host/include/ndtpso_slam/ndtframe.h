@@ -41,6 +41,19 @@ struct NDTAlignRequest {
   bool ok;        // out
 };
 
+// One request of NDTFrame::loadLaserBatch (not in the reference): frame->loadLaser(*laser_data, min_angle, angle_increment, max_range).
+struct NDTLoadRequest {
+  NDTFrame* frame;
+  const vector<float>* laser_data;
+  float min_angle, angle_increment, max_range;
+};
+// One request of NDTFrame::updateBatch (not in the reference): frame->update(trans, new_frame).
+struct NDTUpdateRequest {
+  NDTFrame* frame;
+  Vector3d trans;
+  NDTFrame* new_frame;
+};
+
 class NDTFrame {
  public:
   uint16_t width, height, widthNumOfCells, heightNumOfCells;
@@ -97,6 +110,16 @@ class NDTFrame {
   // result), and so does a frame that one request aligns against and another aligns as scan; any other request takes align() itself, in its place.  The reference aligns one scan at a time
   // (ndtpso_slam_node.cpp:182-194).
   static void alignBatch(NDTAlignRequest* reqs, size_t n);
+  // Several loadLaser() / update() calls at once: observably identical to the member calls in request order -- `built`, the
+  // refusal of an update() after a failed align() with its count (updatesRefused()) and recorded error, the rule for the
+  // speculative build, every error recorded as the member call records it -- but consecutive requests that qualify share their
+  // launches (ndtpso_points_load_scans, ndtpso_map_update_batch, include/ndtpso_hip.h): one launch for the R scan loads of a
+  // fleet step, three for its R map updates.  A request qualifies when its frame is resident and lives in the calling thread's
+  // device context and, for a load, is a one-cell per-scan frame without a map and with room in its scan buffer; for an update,
+  // when the new frame is such a device-resident point list.  A frame that appears a second time in a run -- or as map in one
+  // request and as scan in another -- closes the run; every other request is the member call itself, in its place.
+  static void loadLaserBatch(NDTLoadRequest* reqs, size_t n);
+  static void updateBatch(NDTUpdateRequest* reqs, size_t n);
   // new-frame points in the order cost_function visits them (cells, then insertion; core.cpp:33-36)
   void collectPoints(std::vector<double>& xy) const;
   const NDTPSOConfig& config() const { return s_config; }

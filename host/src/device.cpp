@@ -174,7 +174,9 @@ void release_scan(ndtpso_points* p, uint32_t capacity) {  // (under a Use of the
   if (!g_alive) return;  // the contexts are gone, and the device memory with them
   Ctx* x = active_ctx();
   std::lock_guard<std::recursive_mutex> lock(x->mu);
-  if (x->scan_pool.size() < 8)
+  // (a thread that serves a fleet frees R per-scan frames a step and makes R new ones: a pool of 8 sent the others through
+  // ndtpso_points_destroy / _create, a stream synchronisation and an allocation each, at every step; 64 KB per pooled buffer)
+  if (x->scan_pool.size() < 256)
     x->scan_pool.emplace_back(p, capacity);
   else
     ndtpso_points_destroy(p);

@@ -237,6 +237,17 @@ void NDTFrame::collectPoints(std::vector<double>& xy) const {
   }
 }
 
+namespace {
+bool speculate_after_update() {
+  static const bool speculate = [] {
+    const char* e = std::getenv("NDTPSO_SPECULATE");  // =0: leave every build to the call that asks for it
+    return !(e && e[0] == '0');
+  }();
+  return speculate;
+}
+const char* const kUpdateRefused = "update after a failed align (scan not merged)";
+}  // namespace
+
 // reference: update, ndtframe.cpp:187-198 (transform every slot-0 point of new_frame by `trans`, re-bin here)
 void NDTFrame::update(Vector3d trans, NDTFrame* const new_frame) {
   // The node merges every scan at the pose align() has just returned (ndtpso_slam_node.cpp:194-198) and never asks whether
@@ -248,7 +259,7 @@ void NDTFrame::update(Vector3d trans, NDTFrame* const new_frame) {
   // its global map as well (global_map_->update, ndtpso_slam_node.cpp:202), a frame that never aligns and so never learns of it.
   if (!s_last_align_ok || t_last_align_failed) {
     ++s_updates_refused;
-    ndtpso_host::check(NDTPSO_E_STATE, "update after a failed align (scan not merged)");
+    ndtpso_host::check(NDTPSO_E_STATE, kUpdateRefused);
     return;
   }
   // a frame that lives in another thread's device context: its points travel through the host (collected under ITS context)
@@ -271,11 +282,7 @@ void NDTFrame::update(Vector3d trans, NDTFrame* const new_frame) {
     // A frame that is aligned against gets its cells built and its table packed right away, off the next align()'s
     // critical path; should something other than align / build come first, the device takes the build back
     // (ndtpso_map_speculate_build), so the lazy build of the reference is what every caller still observes.
-    static const bool speculate = [] {
-      const char* e = std::getenv("NDTPSO_SPECULATE");  // =0: leave every build to the call that asks for it
-      return !(e && e[0] == '0');
-    }();
-    if (s_iter > 0 && speculate) ndtpso_host::check(ndtpso_map_speculate_build(m), "update");
+    if (s_iter > 0 && speculate_after_update()) ndtpso_host::check(ndtpso_map_speculate_build(m), "update");
     return;
   }
   std::vector<double> xy;
@@ -681,6 +688,149 @@ void NDTFrame::alignBatch(NDTAlignRequest* reqs, size_t n) {
       f->recordAlignOutcome(ok);
       r.pose = f->recordAlignedPose(ok ? Vector3d(jobs[k].pose[0], jobs[k].pose[1], jobs[k].pose[2]) : r.guess);
       r.ok = ok;
+    }
+    i = j;
+  }
+}
+
+// Several loadLaser() calls (see ndtframe.h): the member's own steps per request, with ONE ndtpso_points_load_scans for a run of
+// requests on per-scan frames.
+void NDTFrame::loadLaserBatch(NDTLoadRequest* reqs, size_t n) {
+  if (!reqs) return;
+  ndtpso_host::Ctx* const mine = ndtpso_host::thread_ctx();
+  auto batchable = [&](const NDTLoadRequest& r) {
+    const NDTFrame* f = r.frame;
+    if (!f || !r.laser_data || r.laser_data->empty()) return false;
+    if (!f->s_resident || f->dev() != mine || f->numOfCells != 1 || f->d_map_) return false;
+    const uint32_t cnt = (uint32_t)r.laser_data->size();
+    return f->d_scan_ ? f->d_scan_upper_ + cnt <= f->d_scan_cap_ : true;  // (a first load sizes the buffer for the scan)
+  };
+  size_t i = 0;
+  while (i < n) {
+    size_t j = i;
+    while (j < n && batchable(reqs[j])) {
+      bool again = false;
+      for (size_t k = i; k < j && !again; ++k) again = reqs[k].frame == reqs[j].frame;
+      if (again) break;
+      ++j;
+    }
+    if (j - i < 2) {  // loadLaser() itself, in its place
+      const NDTLoadRequest& r = reqs[i];
+      if (r.frame && r.laser_data) r.frame->loadLaser(*r.laser_data, r.min_angle, r.angle_increment, r.max_range);
+      ++i;
+      continue;
+    }
+    ndtpso_host::Use use(mine);
+    std::vector<ndtpso_points_load_job> jobs;
+    std::vector<NDTFrame*> owner;
+    jobs.reserve(j - i);
+    for (size_t k = i; k < j; ++k) {
+      const NDTLoadRequest& r = reqs[k];
+      NDTFrame* f = r.frame;
+      const uint32_t cnt = (uint32_t)r.laser_data->size();
+      f->built = false;
+      if (!f->d_scan_) {
+        f->d_scan_cap_ = std::max(kScanCapacity, cnt);
+        f->d_scan_ = ndtpso_host::acquire_scan(f->d_scan_cap_);
+        f->d_scan_upper_ = 0;
+        if (!f->d_scan_) continue;  // no device memory: the scan is dropped (error recorded)
+      }
+      ndtpso_points_load_job job;
+      std::memset(&job, 0, sizeof(job));
+      job.pts = f->d_scan_;
+      job.ranges = r.laser_data->data();
+      job.geom = ndtpso_scan_geom{cnt, r.min_angle, r.angle_increment, r.max_range, f->s_config.laserIgnoreEpsilon};
+      job.trans[0] = f->s_trans.x();
+      job.trans[1] = f->s_trans.y();
+      job.trans[2] = f->s_trans.z();
+      job.clip = grid_of(*f);
+      job.flags = 1u | 2u | (f->d_scan_upper_ > 0 ? 4u : 0u);
+      jobs.push_back(job);
+      owner.push_back(f);
+    }
+    if (!jobs.empty()) {
+      const int rc_call = ndtpso_points_load_scans(ndtpso_host::device(), jobs.data(), (uint32_t)jobs.size());
+      bool some_job_failed = false;
+      for (const ndtpso_points_load_job& job : jobs) some_job_failed = some_job_failed || job.rc != NDTPSO_OK;
+      for (size_t k = 0; k < jobs.size(); ++k)  // (a call refused as a whole failed every request)
+        if (ndtpso_host::check((rc_call != NDTPSO_OK && !some_job_failed) ? rc_call : jobs[k].rc, "loadLaser"))
+          owner[k]->d_scan_upper_ += jobs[k].geom.n_beams;
+    }
+    i = j;
+  }
+}
+
+// Several update() calls (see ndtframe.h): the member's own steps per request, with ONE ndtpso_map_update_batch for a run of
+// requests that merge device-resident scans into resident maps.
+void NDTFrame::updateBatch(NDTUpdateRequest* reqs, size_t n) {
+  if (!reqs) return;
+  ndtpso_host::Ctx* const mine = ndtpso_host::thread_ctx();
+  auto batchable = [&](const NDTUpdateRequest& r) {
+    const NDTFrame* f = r.frame;
+    const NDTFrame* c = r.new_frame;
+    return f && c && f->s_resident && f->dev() == mine && c->dev() == mine && c->s_resident && c->d_scan_ && !c->d_map_;
+  };
+  size_t i = 0;
+  while (i < n) {
+    size_t j = i;
+    while (j < n && batchable(reqs[j])) {
+      bool again = false;
+      for (size_t k = i; k < j && !again; ++k)
+        again = reqs[k].frame == reqs[j].frame || reqs[k].new_frame == reqs[j].frame || reqs[k].frame == reqs[j].new_frame;
+      if (again) break;
+      ++j;
+    }
+    if (j - i < 2) {  // update() itself, in its place
+      const NDTUpdateRequest& r = reqs[i];
+      if (r.frame && r.new_frame) r.frame->update(r.trans, r.new_frame);
+      ++i;
+      continue;
+    }
+    ndtpso_host::Use use(mine);
+    // update()'s steps per request; what each request has to record is recorded in request order behind the call
+    enum { kRefused = -1, kNoMap = -2 };
+    std::vector<ndtpso_map_update_job> jobs;
+    std::vector<int> what(j - i);  // the request's job, or why it has none
+    jobs.reserve(j - i);
+    for (size_t k = i; k < j; ++k) {
+      const NDTUpdateRequest& r = reqs[k];
+      NDTFrame* f = r.frame;
+      if (!f->s_last_align_ok || t_last_align_failed) {  // refused: see update()
+        ++f->s_updates_refused;
+        what[k - i] = kRefused;
+        continue;
+      }
+      f->built = false;
+      ndtpso_map* m = f->ensureMap();
+      if (!m) {
+        what[k - i] = kNoMap;
+        continue;
+      }
+      ndtpso_map_update_job job;
+      std::memset(&job, 0, sizeof(job));
+      job.map = m;
+      job.points = r.new_frame->d_scan_;
+      job.pose[0] = r.trans.x();
+      job.pose[1] = r.trans.y();
+      job.pose[2] = r.trans.z();
+      job.flags = 1u | ((f->s_iter > 0 && speculate_after_update()) ? 2u : 0u);
+      what[k - i] = (int)jobs.size();
+      jobs.push_back(job);
+    }
+    int rc_call = NDTPSO_OK;
+    bool some_job_failed = false;
+    if (!jobs.empty()) {
+      rc_call = ndtpso_map_update_batch(ndtpso_host::device(), jobs.data(), (uint32_t)jobs.size());
+      for (const ndtpso_map_update_job& job : jobs) some_job_failed = some_job_failed || job.rc != NDTPSO_OK;
+    }
+    for (size_t k = i; k < j; ++k) {
+      const int w = what[k - i];
+      if (w == kRefused)
+        ndtpso_host::check(NDTPSO_E_STATE, kUpdateRefused);
+      else if (w == kNoMap)
+        ndtpso_host::check(ndtpso_map_mark_unbuilt(nullptr), "update");
+      else
+        ndtpso_host::check((rc_call != NDTPSO_OK && !some_job_failed) ? rc_call : jobs[(size_t)w].rc, "update");
     }
     i = j;
   }

@@ -320,6 +320,65 @@ _Static_assert(sizeof(ndtpso_map_align_job) == NDTPSO_MAP_ALIGN_JOB_BYTES, "ndtp
 #endif
 int ndtpso_map_align_batch(ndtpso_ctx *ctx, ndtpso_map_align_job *jobs, uint32_t n_jobs,
                            const ndtpso_pso_config *cfg, int score_mode);
+/* Several ndtpso_points_load_scan calls of one context in ONE launch (NDTFrame::loadLaser of the R per-scan frames a process
+ * serves, ndtpso_slam_node.cpp:186; the reference loads one scan at a time).  After the call every ndtpso_points -- its points
+ * in order and its count on the device, the host's upper bound -- is bit for bit what
+ *   ndtpso_points_load_scan(jobs[j].pts, jobs[j].ranges, &jobs[j].geom, trans or NULL, clip or NULL, append)
+ * for j = 0 .. n_jobs - 1 in that order leaves.  All the jobs' ranges travel in one pinned block that the kernel reads in place,
+ * so a call waits for the stream no more often than one single load does, however many jobs it has.  A scan buffer named a
+ * second time closes the current launch (its second load follows its first); a call of one job is the single call.
+ * Returns NDTPSO_E_ARG before anything is enqueued for a null pointer (ctx, jobs, a job's pts or ranges), n_jobs == 0 or a scan
+ * of another context; else NDTPSO_OK if every job's rc is 0, else the first failing job's rc (the other jobs are completed). */
+typedef struct {
+  ndtpso_points *pts;      /* in: the resident scan to load into (may repeat across jobs) */
+  const float *ranges;     /* in: geom.n_beams ranges; free to reuse when the call returns */
+  double trans[3];         /* in: used when flags bit 0 is set */
+  ndtpso_grid clip;        /* in: used when flags bit 1 is set */
+  ndtpso_scan_geom geom;   /* in */
+  uint32_t flags;          /* in: bit 0 = trans given, bit 1 = clip given, bit 2 = append */
+  int32_t rc;              /* out: NDTPSO_OK or this job's error */
+  int32_t reserved;
+} ndtpso_points_load_job;
+#define NDTPSO_POINTS_LOAD_JOB_BYTES 88
+#define NDTPSO_POINTS_LOAD_JOB_RC_OFFSET 80
+/* Several map updates of one context in shared launches (NDTFrame::update of the R maps a process serves,
+ * ndtpso_slam_node.cpp:198; the reference updates one frame at a time): one insert launch, and for the jobs that ask for the
+ * speculative build one build and one pack launch, where the single calls take three launches per map.  After the call every
+ * map is bit for bit in the state that
+ *   ndtpso_map_mark_unbuilt(map); ndtpso_map_insert(map, points, pose or NULL); [ndtpso_map_speculate_build(map);]
+ * for j = 0 .. n_jobs - 1 in that order leaves it in: cells, window terms, every slot's points in order, header, packed table
+ * image, the pinned header of the speculative build and its number on the device; built, the pending speculation, the bounds
+ * of points and pool chunks and the late-binding figures on the host -- so a following ndtpso_map_align or
+ * ndtpso_map_align_batch takes the path it would take after the single calls and returns the same bits.  (Which pool chunk a
+ * point lands in is unordered inside one insert already, and stays so.)
+ * Routing is decided per job, on the host, by the single calls' own rules (they share the code): a job whose preparation must
+ * wait for the device -- a point pool to be measured or grown, an undo log or pinned header to be allocated -- runs through the
+ * single calls in its place in job order (route 0), and so does a call of one job.  A map named a second time closes the
+ * current set of launches, so per map the order is job order.  A pending speculation is taken back ahead of the shared insert,
+ * on the same stream.  An empty scan inserts nothing and still takes the flagged build.
+ * Returns NDTPSO_E_ARG before anything is enqueued for a null pointer, n_jobs == 0 or a map or scan of another context; else
+ * NDTPSO_OK if every job's rc is 0, else the first failing job's rc (the other jobs are completed). */
+typedef struct {
+  ndtpso_map *map;             /* in (may repeat across jobs) */
+  const ndtpso_points *points; /* in: a loaded resident scan */
+  double pose[3];              /* in: used when flags bit 0 is set */
+  uint32_t flags;              /* in: bit 0 = pose given, bit 1 = speculative build afterwards */
+  int32_t rc;                  /* out: NDTPSO_OK or this job's error */
+  int32_t route;               /* out: 1 = the shared launches, 0 = the single calls' path */
+  int32_t reserved;
+} ndtpso_map_update_job;
+#define NDTPSO_MAP_UPDATE_JOB_BYTES 56
+#define NDTPSO_MAP_UPDATE_JOB_RC_OFFSET 44
+#define NDTPSO_MAP_UPDATE_JOB_ROUTE_OFFSET 48
+#if defined(__cplusplus)
+static_assert(sizeof(ndtpso_points_load_job) == NDTPSO_POINTS_LOAD_JOB_BYTES, "ndtpso_points_load_job layout");
+static_assert(sizeof(ndtpso_map_update_job) == NDTPSO_MAP_UPDATE_JOB_BYTES, "ndtpso_map_update_job layout");
+#elif defined(__STDC_VERSION__) && __STDC_VERSION__ >= 201112L
+_Static_assert(sizeof(ndtpso_points_load_job) == NDTPSO_POINTS_LOAD_JOB_BYTES, "ndtpso_points_load_job layout");
+_Static_assert(sizeof(ndtpso_map_update_job) == NDTPSO_MAP_UPDATE_JOB_BYTES, "ndtpso_map_update_job layout");
+#endif
+int ndtpso_points_load_scans(ndtpso_ctx *ctx, ndtpso_points_load_job *jobs, uint32_t n_jobs);
+int ndtpso_map_update_batch(ndtpso_ctx *ctx, ndtpso_map_update_job *jobs, uint32_t n_jobs);
 /* cost_function (core.cpp:26-48) of a loaded scan against the map at n_poses candidate poses (3 doubles each) */
 int ndtpso_map_cost(ndtpso_map *map, ndtpso_points *new_points, const double *poses, uint32_t n_poses, int score_mode,
                     double *costs);

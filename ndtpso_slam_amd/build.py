@@ -14,8 +14,11 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 SRC = os.path.join(HERE, "csrc", "ndtpso_hip.hip")
 # the job kernels of ndtpso_map_align_batch: a translation unit of their own (see the file's header), same flags, same library
 SRC_JOBS = os.path.join(HERE, "csrc", "ndtpso_align_jobs.hip")
-SRCS = [SRC, SRC_JOBS]
-DEPS = [SRC, SRC_JOBS, os.path.join(HERE, "csrc", "ndtpso_kernels.hpp"), os.path.join(HERE, "csrc", "ndtpso_map.inc"),
+# ... and those of ndtpso_points_load_scans / ndtpso_map_update_batch, likewise
+SRC_MAP_JOBS = os.path.join(HERE, "csrc", "ndtpso_map_jobs.hip")
+SRCS = [SRC, SRC_JOBS, SRC_MAP_JOBS]
+DEPS = [SRC, SRC_JOBS, SRC_MAP_JOBS, os.path.join(HERE, "csrc", "ndtpso_map_device.inc"),
+        os.path.join(HERE, "csrc", "ndtpso_map_jobs.h"), os.path.join(HERE, "csrc", "ndtpso_map_update.inc"), os.path.join(HERE, "csrc", "ndtpso_kernels.hpp"), os.path.join(HERE, "csrc", "ndtpso_map.inc"),
         os.path.join(HERE, "csrc", "ndtpso_pairs_body.inc"),
         os.path.join(HERE, "csrc", "ndtpso_align_body.inc"), os.path.join(HERE, "csrc", "ndtpso_map_batch.inc"),
         os.path.join(HERE, "csrc", "ndtpso_device_common.inc"), os.path.join(HERE, "csrc", "ndtpso_align_jobs.h"),

@@ -103,6 +103,18 @@ class MapAlignJob(C.Structure):
                 ("pose", C.c_double * 3), ("cost", C.c_double), ("stats", AlignStats), ("rc", C.c_int32), ("route", C.c_int32)]
 
 
+class PointsLoadJob(C.Structure):
+    """ndtpso_points_load_job (include/ndtpso_hip.h): one scan load of ndtpso_points_load_scans"""
+    _fields_ = [("pts", C.c_void_p), ("ranges", C.POINTER(C.c_float)), ("trans", C.c_double * 3), ("clip", Grid),
+                ("geom", ScanGeom), ("flags", C.c_uint32), ("rc", C.c_int32), ("reserved", C.c_int32)]
+
+
+class MapUpdateJob(C.Structure):
+    """ndtpso_map_update_job (include/ndtpso_hip.h): one map update of ndtpso_map_update_batch"""
+    _fields_ = [("map", C.c_void_p), ("points", C.c_void_p), ("pose", C.c_double * 3), ("flags", C.c_uint32),
+                ("rc", C.c_int32), ("route", C.c_int32), ("reserved", C.c_int32)]
+
+
 STATS_DTYPE = np.dtype([("n_points", "<u4"), ("n_built", "<u4"), ("cost_evals", "<u4"), ("rounds", "<u4"),
                         ("gbest_updates", "<u4"), ("status", "<u2"), ("arbitrated", "<u2"), ("t_start", "<u4"),
                         ("t_end", "<u4")])   # the C struct's `status` word: flags in its low half, SCORE_EXACT's count above
@@ -118,7 +130,7 @@ EXPORTS = [
     "ndtpso_points_create", "ndtpso_points_destroy", "ndtpso_points_load_scan", "ndtpso_points_set", "ndtpso_points_get",
     "ndtpso_map_create", "ndtpso_map_destroy", "ndtpso_map_reset", "ndtpso_map_clear", "ndtpso_map_mark_unbuilt", "ndtpso_map_insert", "ndtpso_map_insert_host",
     "ndtpso_map_build", "ndtpso_map_speculate_build", "ndtpso_map_align", "ndtpso_map_cost", "ndtpso_map_get_info", "ndtpso_map_get_cells", "ndtpso_map_get_points",
-    "ndtpso_map_get_occupancy", "ndtpso_map_align_batch",
+    "ndtpso_map_get_occupancy", "ndtpso_map_align_batch", "ndtpso_points_load_scans", "ndtpso_map_update_batch",
     "ndtpso_shard_group_create", "ndtpso_shard_group_destroy", "ndtpso_shard_group_size", "ndtpso_shard_last_error",
     "ndtpso_shard_range", "ndtpso_align_pairs_sharded", "ndtpso_align_pairs_sharded_dev", "ndtpso_shard_last_timing",
     "ndtpso_shard_gathered", "ndtpso_shard_group_describe", "ndtpso_shard_verify_gather",
@@ -224,6 +236,8 @@ def load(build_if_missing: bool = True):
     L.ndtpso_map_align.argtypes = [vp, vp, dp, dp, C.POINTER(PSOConfig), C.c_uint32, ip, C.c_int, dp, dp,
                                    C.POINTER(AlignStats)]
     L.ndtpso_map_align_batch.argtypes = [vp, C.POINTER(MapAlignJob), C.c_uint32, C.POINTER(PSOConfig), C.c_int]
+    L.ndtpso_points_load_scans.argtypes = [vp, C.POINTER(PointsLoadJob), C.c_uint32]
+    L.ndtpso_map_update_batch.argtypes = [vp, C.POINTER(MapUpdateJob), C.c_uint32]
     L.ndtpso_exact_check_jobs.argtypes = [vp, C.POINTER(C.c_int)]
     L.ndtpso_map_cost.argtypes = [vp, vp, dp, C.c_uint32, C.c_int, dp]
     L.ndtpso_map_get_info.argtypes = [vp, C.POINTER(MapInfo)]
@@ -650,6 +664,52 @@ def align_maps(ctx: "Context", jobs, cfg: PSOConfig, mode=SCORE_F32):
         st[i] = np.frombuffer(bytes(j.stats), dtype=STATS_DTYPE)[0]
     route = np.array([j.route for j in arr[:n]], dtype=np.int32)
     return poses, costs, {k: st[k].copy() for k in STATS_DTYPE.names}, rcs, route
+
+
+def load_scans(ctx: "Context", jobs):
+    """ndtpso_points_load_scans: the scan loads of `jobs` -- (ResidentScan, ranges, ScanGeom, trans | None, clip Grid | None, append)
+    each -- in one launch.  Returns rc [J].  Raises only for the call's own errors (bad arguments); a job's failure is its rc."""
+    n = len(jobs)
+    arr = (PointsLoadJob * max(n, 1))()
+    keep = []
+    for j, (scan, ranges, geom, trans, clip, append) in zip(arr, jobs):
+        r = np.ascontiguousarray(ranges, dtype=np.float32)
+        assert r.size == geom.n_beams
+        keep.append(r)
+        j.pts, j.ranges, j.geom = scan._h, _p(r, C.c_float), geom
+        if trans is not None:
+            j.trans[:] = [float(v) for v in _f64(trans, 3)]
+            j.flags |= 1
+        if clip is not None:
+            j.clip = clip
+            j.flags |= 2
+        if append:
+            j.flags |= 4
+    rc = ctx._lib.ndtpso_points_load_scans(ctx._h, arr, n)
+    rcs = np.array([j.rc for j in arr[:n]], dtype=np.int32)
+    if rc != OK and not (rcs != OK).any():
+        ctx._chk(rc)
+    return rcs
+
+
+def update_maps(ctx: "Context", jobs):
+    """ndtpso_map_update_batch: the map updates of `jobs` -- (ResidentMap, ResidentScan, pose | None, speculate) each: mark_unbuilt,
+    insert at the pose, and with `speculate` the speculative build -- in shared launches.  Returns rc [J] and route [J] (1: the
+    shared launches, 0: the single calls' path).  Raises only for the call's own errors; a job's failure is its rc."""
+    n = len(jobs)
+    arr = (MapUpdateJob * max(n, 1))()
+    for j, (m, scan, pose, speculate) in zip(arr, jobs):
+        j.map, j.points = m._h, scan._h
+        if pose is not None:
+            j.pose[:] = [float(v) for v in _f64(pose, 3)]
+            j.flags |= 1
+        if speculate:
+            j.flags |= 2
+    rc = ctx._lib.ndtpso_map_update_batch(ctx._h, arr, n)
+    rcs = np.array([j.rc for j in arr[:n]], dtype=np.int32)
+    if rc != OK and not (rcs != OK).any():
+        ctx._chk(rc)
+    return rcs, np.array([j.route for j in arr[:n]], dtype=np.int32)
 
 
 class ResidentScan:

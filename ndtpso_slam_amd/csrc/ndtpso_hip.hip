@@ -618,6 +618,7 @@ struct ndtpso_ctx {
   size_t jobs_pinned_cap = 0;
   DevBuf jobs_out, jobs_table;
   uint32_t jobs_issued = 0;
+  bool map_jobs_big_lds = false;      // ndtpso_map_update_batch: k_map_pack_jobs may take the whole LDS (set once per context)
 };
 
 namespace {
