@@ -11,19 +11,23 @@ import shutil
 import subprocess
 
 HERE = os.path.dirname(os.path.abspath(__file__))
-SRC = os.path.join(HERE, "csrc", "ndtpso_hip.hip")
-# the job kernels of ndtpso_map_align_batch: a translation unit of their own (see the file's header), same flags, same library
-SRC_JOBS = os.path.join(HERE, "csrc", "ndtpso_align_jobs.hip")
-# ... and those of ndtpso_points_load_scans / ndtpso_map_update_batch, likewise
-SRC_MAP_JOBS = os.path.join(HERE, "csrc", "ndtpso_map_jobs.hip")
-SRCS = [SRC, SRC_JOBS, SRC_MAP_JOBS]
-DEPS = [SRC, SRC_JOBS, SRC_MAP_JOBS, os.path.join(HERE, "csrc", "ndtpso_map_device.inc"),
-        os.path.join(HERE, "csrc", "ndtpso_map_jobs.h"), os.path.join(HERE, "csrc", "ndtpso_map_update.inc"), os.path.join(HERE, "csrc", "ndtpso_kernels.hpp"), os.path.join(HERE, "csrc", "ndtpso_map.inc"),
-        os.path.join(HERE, "csrc", "ndtpso_pairs_body.inc"),
-        os.path.join(HERE, "csrc", "ndtpso_align_body.inc"), os.path.join(HERE, "csrc", "ndtpso_map_batch.inc"),
-        os.path.join(HERE, "csrc", "ndtpso_device_common.inc"), os.path.join(HERE, "csrc", "ndtpso_align_jobs.h"),
-        os.path.join(HERE, "csrc", "ndtpso_shard.inc"), os.path.join(HERE, "csrc", "ndtpso_selftest.inc"),
-        os.path.join(os.path.dirname(HERE), "include", "ndtpso_hip.h")]
+CSRC = os.path.join(HERE, "csrc")
+
+
+def _listed(name: str) -> list:
+    with open(os.path.join(CSRC, name)) as f:
+        return [line.strip() for line in f if line.strip()]
+
+
+# What is compiled, and how, is written once, in two plain lists next to the sources -- one item per line -- which
+# host/CMakeLists.txt reads as well (tests/test_build_recipes.py holds the two recipes together):
+#   csrc/hip_units.txt   the translation units: the C-ABI with the alignment kernels, and the job kernels of the batched
+#                        entries in units of their own (see those files' headers) -- same flags, same library
+#   csrc/hip_flags.txt   the flags of every build of the library
+# A build depends on every file under csrc/ (units, what they include, the two lists) and on the C header.
+SRCS = [os.path.join(CSRC, u) for u in _listed("hip_units.txt")]
+DEPS = sorted(os.path.join(CSRC, f) for f in os.listdir(CSRC) if os.path.isfile(os.path.join(CSRC, f))) + \
+    [os.path.join(os.path.dirname(HERE), "include", "ndtpso_hip.h")]
 LIB_DIR = os.path.join(HERE, "lib")
 LIB = os.path.join(LIB_DIR, "libndtpso_hip.so")
 
@@ -34,8 +38,8 @@ LIB = os.path.join(LIB_DIR, "libndtpso_hip.so")
 # sources without IPRA, and every other build without it, are right (NOTEBOOK, "The unit form on swarms kept in HBM";
 # tests/test_gpu_fullsize.py::test_unit_form_on_swarms_kept_in_hbm).  Cost: 4 % of the exact kernel when the switch was made,
 # nothing measurable on the round's final kernels.
-FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fno-fast-math",
-         "-mllvm", "-enable-ipra=0", "-fPIC", "-shared", "-Wall", "-Wno-unused-function"]
+# (the warnings are this recipe's alone: a tree that pulls the library in through CMake is not told about ours)
+FLAGS = _listed("hip_flags.txt") + ["-Wall", "-Wno-unused-function"]
 
 
 def hipcc() -> str:

@@ -799,8 +799,16 @@ constexpr uint32_t launch_code(bool f64, int path, bool cl, bool arb, bool nocli
 // table only -- a long-lived map can hold more built cells than LDS has room for).
 // big_table (fused pairs kernel, a redo launch): the largest table a workgroup can hold, whatever that does to the number of
 // workgroups per compute unit -- for the alignments whose box did not fit the table of the first launch
-bool make_plan(int mode, const GridP& g, const WinP& wn, int n_max, int P, Plan* plan, bool dynamic_window = false,
-               bool allow_dense = true, bool allow_global = false, bool exact = false, bool big_table = false) {
+struct PlanAsk {
+  bool dynamic_window = false;  // the fused pairs kernel: `wn` is the static range box, the dense table sized per alignment
+  bool allow_dense = true;
+  bool allow_global = false;
+  bool exact = false;           // the swarm keeps the arbitration's four arrays
+  bool big_table = false;
+};
+bool make_plan(int mode, const GridP& g, const WinP& wn, int n_max, int P, const PlanAsk& ask, Plan* plan) {
+  const bool dynamic_window = ask.dynamic_window, allow_dense = ask.allow_dense, allow_global = ask.allow_global, exact = ask.exact,
+             big_table = ask.big_table;
   const int bitmap_path = g.cs_pow2 ? 1 : 0;
   plan->shrunk = false;
   plan->boxy = false;
@@ -942,6 +950,44 @@ void launch_pairs_gated(dim3 grid, dim3 block, int lds, hipStream_t stream, Args
 int check_pso(ndtpso_ctx* ctx, const ndtpso_pso_config* cfg) {
   if (!cfg || cfg->population < 1 || cfg->iterations < 0) return fail(ctx, NDTPSO_E_ARG, "bad PSO config");
   return NDTPSO_OK;
+}
+int check_mode(ndtpso_ctx* ctx, int mode) {
+  if (mode != NDTPSO_SCORE_F32 && mode != NDTPSO_SCORE_F64 && mode != NDTPSO_SCORE_EXACT) return fail(ctx, NDTPSO_E_ARG, "bad score mode");
+  return NDTPSO_OK;
+}
+
+// The score mode a table is aligned with, and its plan.  The exact mode is the fp32 score with arbitration where the table
+// takes the dense form (plan.path == 2), else the fp64 score itself; the other two modes run as asked.  `ok`: the plan fits
+// (make_plan); the plan of a failure is still the last form tried.  What a caller refuses beyond that -- a swarm in HBM, a form
+// its kernels do not have -- it says itself, at the call.
+struct ScorePlan {
+  bool ok;
+  int mode;         // NDTPSO_SCORE_F32 or NDTPSO_SCORE_F64
+  bool arbitrates;  // the fp32 score, arbitrating in fp64
+  Plan plan;
+};
+ScorePlan resolve_score_plan(int asked, const GridP& g, const WinP& wn, int n_max, int P, PlanAsk ask) {
+  ScorePlan r;
+  r.mode = asked;
+  r.arbitrates = false;
+  if (asked == NDTPSO_SCORE_EXACT) {
+    ask.exact = true;
+    if (make_plan(NDTPSO_SCORE_F32, g, wn, n_max, P, ask, &r.plan) && r.plan.path == 2) {
+      r.ok = r.arbitrates = true;
+      r.mode = NDTPSO_SCORE_F32;
+      return r;
+    }
+    r.mode = NDTPSO_SCORE_F64;
+    ask.exact = false;
+  }
+  r.ok = make_plan(r.mode, g, wn, n_max, P, ask, &r.plan);
+  return r;
+}
+// a table built ahead of the alignment (k_align, k_cost_batch, the job kernels): either form in LDS, else read from its HBM image
+PlanAsk prebuilt_table_ask() {
+  PlanAsk ask;
+  ask.allow_global = true;
+  return ask;
 }
 
 int exact_mode_resolve(ndtpso_ctx* c, int* mode);  // ndtpso_selftest.inc: the start-up check of NDTPSO_SCORE_EXACT
@@ -1424,7 +1470,7 @@ int ndtpso_cells_build_windowed(ndtpso_ctx* c, uint32_t n_cells, ndtpso_cell_win
 static int cost_launch(ndtpso_ctx* c, const unsigned char* image, const GridP& g, const WinP& wn, const double2* d_xy,
                        uint32_t n, const double* poses, uint32_t m, int mode, double* costs, int32_t* cell_idx) {
   Plan plan;
-  if (!make_plan(mode, g, wn, std::max<int>((int)n, 1), 0, &plan, false, true, true))
+  if (!make_plan(mode, g, wn, std::max<int>((int)n, 1), 0, prebuilt_table_ask(), &plan))
     return fail(c, NDTPSO_E_CAPACITY, "points do not fit in LDS");
   const Layout& L = plan.L;
   HIP_TRY(c, c->poses.reserve((size_t)m * 24));
@@ -1473,7 +1519,7 @@ static int cost_launch(ndtpso_ctx* c, const unsigned char* image, const GridP& g
 int ndtpso_cost_batch(ndtpso_ctx* c, const double* xy, uint32_t n, const double* poses, uint32_t m, int mode,
                       double* costs, int32_t* cell_idx) {
   if (!c || (!xy && n) || !poses || !costs || m == 0) return fail(c, NDTPSO_E_ARG, "null argument");
-  if (mode != NDTPSO_SCORE_F32 && mode != NDTPSO_SCORE_F64 && mode != NDTPSO_SCORE_EXACT) return fail(c, NDTPSO_E_ARG, "bad score mode");
+  if (int rc = check_mode(c, mode)) return rc;
   if (!c->have_ref) return fail(c, NDTPSO_E_STATE, "no reference table");
   if (mode == NDTPSO_SCORE_EXACT) mode = NDTPSO_SCORE_F64;  // a cost has nothing to arbitrate: the fp64 score (as ndtpso_map_cost)
   HIP_TRY(c, hipSetDevice(c->device));
@@ -1809,21 +1855,12 @@ static bool must_redo_alone(const AlignStats& st) { return (st.status & (kStatus
 static int align_once(ndtpso_ctx* c, const AlignSrc& src, const ndtpso_pso_config* cfg, uint32_t seed, bool have_table,
                       int mode, double host[kResultDoubles], bool allow_cluster = true,
                       AfterLaunch after = AfterLaunch{nullptr, nullptr}) {
-  Plan plan;
   const uint32_t n = src.n;
-  // exact mode: the fp32-score kernel with arbitration where the table takes the dense form, else the fp64 score itself
-  int exact = 0;
-  if (mode == NDTPSO_SCORE_EXACT) {
-    if (!make_plan(NDTPSO_SCORE_F32, src.g, src.wn, std::max<int>((int)n, 1), cfg->population, &plan, false, true, true, true) ||
-        plan.path != 2) {
-      mode = NDTPSO_SCORE_F64;
-    } else {
-      mode = NDTPSO_SCORE_F32;
-      exact = 1;
-    }
-  }
-  if (!make_plan(mode, src.g, src.wn, std::max<int>((int)n, 1), cfg->population, &plan, false, true, true, exact != 0))
-    return fail(c, NDTPSO_E_CAPACITY, "points + swarm do not fit in LDS");
+  const ScorePlan resolved = resolve_score_plan(mode, src.g, src.wn, std::max<int>((int)n, 1), cfg->population, prebuilt_table_ask());
+  if (!resolved.ok) return fail(c, NDTPSO_E_CAPACITY, "points + swarm do not fit in LDS");
+  const Plan& plan = resolved.plan;
+  const bool exact = resolved.arbitrates;
+  mode = resolved.mode;
   if (src.late_hdr && plan.path != 2) return fail(c, NDTPSO_E_STATE, "late window binding needs the dense form");  // (the caller probes)
   const Layout& L = plan.L;
   double* d_out = (double*)c->out.p;  // [0..2] pose, [3] cost, then stats
@@ -1943,7 +1980,7 @@ static int align_points(ndtpso_ctx* c, const double* xy, uint32_t n, const doubl
                         const ndtpso_pso_config* cfg, uint32_t seed, const int32_t* rand_table, int mode, double out_pose[3],
                         double* out_cost, ndtpso_align_stats* stats, bool allow_cluster) {
   if (!c || (!xy && n) || !guess || !deviation || !out_pose) return fail(c, NDTPSO_E_ARG, "null argument");
-  if (mode != NDTPSO_SCORE_F32 && mode != NDTPSO_SCORE_F64 && mode != NDTPSO_SCORE_EXACT) return fail(c, NDTPSO_E_ARG, "bad score mode");
+  if (int rc = check_mode(c, mode)) return rc;
   if (int rc = check_pso(c, cfg)) return rc;
   if (!c->have_ref) return fail(c, NDTPSO_E_STATE, "no reference table");
   if (int rc = exact_mode_resolve(c, &mode)) return rc;
@@ -1981,519 +2018,7 @@ static int align_finish(ndtpso_ctx* c, const AlignSrc& src, const ndtpso_pso_con
 
 // ---- fused pairs -----------------------------------------------------------------------------------
 
-static int pairs_plan(const ndtpso_scan_geom* geom, const ndtpso_grid* grid, const ndtpso_pso_config* cfg, int mode,
-                      unsigned n_pairs, GridP* g, WinP* wn, Plan* plan, int* waves, bool allow_dense = true,
-                      unsigned n_cus = 0, bool exact = false, bool big_table = false) {
-  if (!geom || geom->n_beams == 0 || !cfg || cfg->population < 1 || cfg->iterations < 0) return NDTPSO_E_ARG;
-  if (make_grid(grid, g) != NDTPSO_OK) return NDTPSO_E_ARG;
-  const double r = (double)geom->max_range;
-  *wn = make_window(*g, -r, r, -r, r, (int)(geom->n_beams / 3) + 1);
-  const bool ok = make_plan(mode, *g, *wn, (int)geom->n_beams, cfg->population, plan, true, allow_dense, false, exact, big_table);
-  *waves = pick_waves(cfg->population, plan->L.total, n_pairs, n_cus);
-  return ok ? NDTPSO_OK : NDTPSO_E_CAPACITY;
-}
-
-int ndtpso_align_pairs_footprint(const ndtpso_scan_geom* geom, const ndtpso_grid* grid, const ndtpso_pso_config* cfg,
-                                 uint32_t* lds_bytes, uint32_t* block_threads) {
-  GridP g;
-  WinP wn;
-  Plan plan;
-  int waves = 0;
-  const int rc = pairs_plan(geom, grid, cfg, NDTPSO_SCORE_F32, 512u, &g, &wn, &plan, &waves);
-  if (rc == NDTPSO_E_ARG) return rc;
-  if (lds_bytes) *lds_bytes = (rc == NDTPSO_OK) ? (uint32_t)plan.L.total : 0u;
-  if (block_threads) *block_threads = (uint32_t)waves * 64u;
-  return rc;
-}
-
-int ndtpso_align_pairs_describe(const ndtpso_scan_geom* geom, const ndtpso_grid* grid, const ndtpso_pso_config* cfg,
-                                int mode, uint32_t n_pairs, ndtpso_pairs_plan* out) {
-  if (!out || (mode != NDTPSO_SCORE_F32 && mode != NDTPSO_SCORE_F64 && mode != NDTPSO_SCORE_EXACT)) return NDTPSO_E_ARG;
-  const bool exact = mode == NDTPSO_SCORE_EXACT;
-  if (exact) mode = NDTPSO_SCORE_F32;  // the same table forms; the swarm keeps four more arrays
-  std::memset(out, 0, sizeof(*out));
-  GridP g;
-  WinP wn;
-  Plan plan;
-  int waves = 0;
-  const int rc = pairs_plan(geom, grid, cfg, mode, n_pairs, &g, &wn, &plan, &waves, true, 0, exact);
-  if (rc == NDTPSO_E_ARG) return rc;
-  out->block_threads = (uint32_t)waves * 64u;
-  out->window_w = (uint32_t)wn.w;
-  out->window_h = (uint32_t)wn.h;
-  if (rc != NDTPSO_OK) return rc;
-  out->lds_bytes = (uint32_t)plan.L.total;
-  out->table_form = (uint32_t)plan.path;
-  out->swarm_in_hbm = (uint32_t)plan.L.swarm_global;
-  out->workgroups_per_cu = (uint32_t)std::max(1, std::min(kMaxLds / plan.L.total, 16 / waves));
-  if (path_is_dense64(plan.path))
-    out->table_bytes = (uint32_t)(plan.L.pts_off - plan.L.drec_off - kImageHeaderBytes);
-  else
-    out->table_bytes = (uint32_t)(plan.L.pts_off - (plan.path == 2 ? 0 : plan.L.bm_off) - (plan.path == 2 ? kCtrlBytes + kImageHeaderBytes : 0));
-  return NDTPSO_OK;
-}
-
-static int launch_pairs(ndtpso_ctx* c, uint32_t n_pairs, const float* d_ref, const float* d_new,
-                        const ndtpso_scan_geom* geom, const ndtpso_grid* grid, const double* d_guess, const double* d_dev,
-                        const ndtpso_pso_config* cfg, const uint32_t* d_seeds, const int32_t* d_tables, int mode,
-                        double* d_pose, double* d_cost, AlignStats* d_stats, uint32_t gate, bool allow_dense,
-                        int* path_out, bool allow_cluster = false, bool exact = false, bool big_table = false,
-                        bool* shrunk_out = nullptr, uint32_t* fb = nullptr,
-                        // a redo launch on clusters: `redo_units` clusters, cluster i taking pair redo_list[1 + i] if i < redo_list[0]
-                        // (k_redo_list), clearing the flags `redo_mask` of the pairs it completes; E_STATE: no cluster shape for this
-                        const uint32_t* redo_list = nullptr, uint32_t redo_units = 0, uint32_t redo_mask = 0) {
-  if (!cfg || cfg->population < 1) return fail(c, NDTPSO_E_ARG, "bad scan/grid/PSO configuration");
-  // a batch smaller than the device: the idle compute units join in, K workgroups per alignment (ClusterP)
-  int K = 1, cw = 4;
-  if (t_plan_force.cluster >= 0) allow_cluster = t_plan_force.cluster != 0;
-  const uint32_t n_units = redo_list ? redo_units : n_pairs;  // alignments this launch provides for (scratch, exchange slots, grid)
-  cluster_launch_k(c, cfg->population, n_units, allow_cluster && gate == 0, true, &K, &cw);
-  if (redo_list && K < 2) return NDTPSO_E_STATE;  // (not an error of the call: the gated launches serve the pairs)
-  GridP g;
-  WinP wn;
-  Plan plan;
-  int waves = 0;
-  // (the fp64 score's dense form runs one workgroup per alignment: a cluster keeps the bitmap form)
-  const int rc = pairs_plan(geom, grid, cfg, mode, n_units, &g, &wn, &plan, &waves,
-                            allow_dense && !(mode == NDTPSO_SCORE_F64 && K > 1), (unsigned)c->n_cus, exact, big_table);
-  if (path_out) *path_out = plan.path;
-  if (shrunk_out) *shrunk_out = plan.shrunk;
-  if (rc == NDTPSO_E_ARG) return fail(c, rc, "bad scan/grid/PSO configuration");
-  if (rc == NDTPSO_E_CAPACITY) return redo_list ? NDTPSO_E_STATE : fail(c, rc, "scan pair working set does not fit in LDS");
-  if (redo_list && plan.L.swarm_global) return NDTPSO_E_STATE;  // (a cluster keeps its swarm in LDS)
-  ScanP sp;
-  const double2* dirs = nullptr;
-  if (int rc = make_scan(c, geom, &sp, &dirs)) return rc;
-  if (K > 1) waves = cw;
-  PsoP ps = make_pso(cfg, waves, mode, plan.L.swarm_global != 0);
-  ClusterP cl;
-  int lds_total = plan.L.total;
-  size_t unit_slots = 0;
-  cluster_launch_shape(c, cfg->population, K, waves, n_units, 0, redo_list, redo_mask, &lds_total, &ps, &cl, &unit_slots);
-  if (K > 1)
-    if (int rc = cluster_slots(c, (size_t)n_units * unit_slots * sizeof(uint4), &cl.xc)) return rc;
-  const size_t stride = ndtpso_rand_draws(cfg);
-  const size_t ws_stride = plan.L.swarm_global ? (size_t)swarm_bytes(cfg->population, true, true) : 0;
-  if (ws_stride) HIP_TRY(c, c->ws.reserve(ws_stride * n_units * (size_t)K));
-  // exact mode on the dense form: one fp64 table image per workgroup in HBM (bitmap of the per-alignment window, mean,
-  // ab, cd), written by the table build and read by the arbitration only
-  size_t ximg_stride = 0;
-  if (exact && mode == NDTPSO_SCORE_F32 && plan.path == 2) {
-    ximg_stride = (size_t)round_up(image_bytes(plan.dense_cap / 32 + 2, wn.rec_cap), 256);
-    HIP_TRY(c, c->ximg.reserve(ximg_stride * n_units * (size_t)K));
-  }
-  unsigned char* d_ximg = ximg_stride ? (unsigned char*)c->ximg.p : nullptr;
-  // a gated launch of a kernel that strides (gate_strides): eight workgroups, or twice the pairs the last gated launch of this
-  // kind found flagged (its workgroup 0 leaves the count in the context's pinned feedback block, words 4 .. 7 by kind); a stale
-  // or foreign count only changes how many workgroups share the flagged pairs
-  uint32_t* gate_fb = nullptr;
-  uint32_t gate_grid = n_pairs;
-  if (gate != 0 && c->pairs_fb) {
-    gate_fb = c->pairs_fb + 4 + ((mode == NDTPSO_SCORE_F64 ? 2 : 0) | (allow_dense ? 1 : 0));
-    const uint32_t seen = __atomic_load_n(gate_fb, __ATOMIC_RELAXED);
-    gate_grid = std::min<uint32_t>(n_pairs, std::max<uint32_t>(8u, 2u * seen));
-    if (const char* e = std::getenv("NDTPSO_GATE_GRID")) gate_grid = std::min<uint32_t>(n_pairs, (uint32_t)std::max(1, std::atoi(e)));  // (diagnostics)
-  }
-  // Two items per wave (eval_pair_half, k_align_pairs<..., PAIR>): short scans with enough particles per wave.  What a pair
-  // saves is around the trips (a third of a six-chunk evaluation, a tenth of a seventeen-chunk one); what it costs is at a
-  // phase's end, where the waves wait for the last of units twice as long -- the fewer items a wave has per phase, the more.
-  // Measured break-even, 8 waves (512 pairs, 0.5 m cells; scripts/pair_items_ab.py): 181 beams any swarm (+ 5-20 %), 361 beams
-  // from 16 particles (+ 6 % there, + 15-21 % from 70), 541 beams from 30 (+ 1 %; + 6-10 % from 70), nothing at 721; fitted as
-  // particles >= (5 (chunks - 3) + 1) waves / 8 for up to nine chunks.  NDTPSO_PAIR_ITEMS=0: never; NDTPSO_PAIR_MAX_BEAMS
-  // (diagnostics): whatever the swarm, up to that many beams.
-  const char* pair_env = std::getenv("NDTPSO_PAIR_ITEMS");
-  static const int pair_max_beams = [] {
-    const char* e = std::getenv("NDTPSO_PAIR_MAX_BEAMS");
-    return e ? std::max(0, std::atoi(e)) : -1;
-  }();
-  const int pair_chunks = ((int)geom->n_beams + 63) / 64;
-  const bool pair_pays = pair_max_beams >= 0 ? (int)geom->n_beams <= pair_max_beams
-                                             : (pair_chunks <= 9 && cfg->population * 8 >= (5 * (pair_chunks - 3) + 1) * waves);
-  const bool pair_items = t_plan_force.pair >= 0 ? t_plan_force.pair != 0 : (!(pair_env && pair_env[0] == '0') && pair_pays);
-#define LAUNCH_PAIRS_CANSB(MODE, PATH, CL, ARB, NOCLIP, SWARM, BOX)                                                \
-  do {                                                                                                             \
-    if (gate == 0 && !redo_list) t_last_launch = launch_code(MODE == kScoreF64, PATH, CL, ARB, NOCLIP, SWARM, BOX, true, pair_items && pair_items_kernel<MODE, PATH, CL, NOCLIP, SWARM, BOX>()); \
-    if (gate != 0 && gate_strides<MODE, PATH, CL>() && gate_fb) {                                                  \
-      launch_pairs_gated<MODE, PATH, CL, ARB, NOCLIP, SWARM, BOX>(dim3(gate_grid), dim3(waves * 64), lds_total, c->stream, d_ref, d_new, \
-                       sp, g, wn, plan.L, plan.dn, plan.dense_cap, ps, d_guess, d_dev, d_seeds, d_tables, stride,   \
-                       (unsigned char*)c->ws.p, ws_stride, d_pose, d_cost, d_stats, gate, cl, dirs, d_ximg,        \
-                       ximg_stride, fb, n_pairs, gate_fb);                                                         \
-    } else if (pair_items && gate == 0 && pair_items_kernel<MODE, PATH, CL, NOCLIP, SWARM, BOX>()) {               \
-      launch_pairs_pair_items<MODE, PATH, CL, ARB, NOCLIP, SWARM, BOX>(dim3(n_pairs), dim3(waves * 64), lds_total, \
-                           c->stream, d_ref, d_new, sp, g, wn, plan.L, plan.dn, plan.dense_cap, ps, d_guess, d_dev, \
-                           d_seeds, d_tables, stride, (unsigned char*)c->ws.p, ws_stride, d_pose, d_cost, d_stats, gate, \
-                           cl, dirs, d_ximg, ximg_stride, fb);                                                     \
-    } else {                                                                                                       \
-      hipLaunchKernelGGL((k_align_pairs<MODE, PATH, CL, ARB, NOCLIP, SWARM, BOX>),                                 \
-                         dim3(CL ? cluster_grid(cl) : n_pairs), dim3(waves * 64), lds_total,                       \
-                         c->stream, d_ref, d_new, sp, g, wn, plan.L, plan.dn, plan.dense_cap, ps, d_guess, d_dev, \
-                         d_seeds, d_tables, stride, (unsigned char*)c->ws.p, ws_stride, d_pose, d_cost, d_stats, gate, \
-                         cl, dirs, d_ximg, ximg_stride, fb);                                                       \
-    }                                                                                                              \
-  } while (0)
-// (a table much smaller than the static window -- Plan::boxy -- and the swarm in LDS: the copies that carry the box guard)
-#define LAUNCH_PAIRS_CANS(MODE, PATH, CL, ARB, NOCLIP, SWARM)                                                      \
-  do {                                                                                                             \
-    if constexpr ((PATH == 2 || PATH == 3) && !CL && SWARM != 1) {                                                 \
-      if (plan.boxy && !plan.L.swarm_global) LAUNCH_PAIRS_CANSB(MODE, PATH, CL, ARB, NOCLIP, SWARM, true);         \
-      else LAUNCH_PAIRS_CANSB(MODE, PATH, CL, ARB, NOCLIP, SWARM, false);                                          \
-    } else {                                                                                                       \
-      LAUNCH_PAIRS_CANSB(MODE, PATH, CL, ARB, NOCLIP, SWARM, false);                                               \
-    }                                                                                                              \
-  } while (0)
-// (the kernels without clipping trips exist per home of the swarm, the others carry both copies of the PSO)
-#define LAUNCH_PAIRS_CAN(MODE, PATH, CL, ARB, NOCLIP)                                    \
-  do {                                                                                   \
-    if constexpr (NOCLIP) {                                                              \
-      if (plan.L.swarm_global) LAUNCH_PAIRS_CANS(MODE, PATH, CL, ARB, NOCLIP, (NOCLIP ? 1 : 2)); \
-      else LAUNCH_PAIRS_CANS(MODE, PATH, CL, ARB, NOCLIP, (NOCLIP ? 0 : 2));             \
-    } else {                                                                             \
-      LAUNCH_PAIRS_CANS(MODE, PATH, CL, ARB, NOCLIP, 2);                                 \
-    }                                                                                    \
-  } while (0)
-// the dense-form kernels on one workgroup per alignment come in a variant without the frame-clipping trips, for grids
-// whose cells do not overhang the frame (DenseP::clip == 0: the usual case) -- less code inlined, better registers:
-// + 3 % in both the fp32 and the exact mode.  (Dropping the copy of the PSO that keeps its swarm in HBM as well took the
-// fp32 kernel to 0 spills and + 0.5 %, the exact one from 61 to 36 spills and - 2 %: left in.)
-#define LAUNCH_PAIRS_CA(MODE, PATH, CL, ARB)                                              \
-  do {                                                                                    \
-    if ((PATH == 3 || PATH == 2) && !CL && !plan.dn.clip) LAUNCH_PAIRS_CAN(MODE, PATH, CL, ARB, ((PATH == 3 || PATH == 2) && !CL)); \
-    else LAUNCH_PAIRS_CAN(MODE, PATH, CL, ARB, false);                                    \
-  } while (0)
-#define LAUNCH_PAIRS_C(MODE, PATH, CL) LAUNCH_PAIRS_CA(MODE, PATH, CL, false)
-#define LAUNCH_PAIRS(MODE, PATH) \
-  do { if (K > 1) LAUNCH_PAIRS_C(MODE, PATH, true); else LAUNCH_PAIRS_C(MODE, PATH, false); } while (0)
-#define LAUNCH_PAIRS_X(PATH) \
-  do { if (K > 1) LAUNCH_PAIRS_CA(kScoreF32, PATH, true, true); else LAUNCH_PAIRS_CA(kScoreF32, PATH, false, true); } while (0)
-  // dense form: when every record lies below 64 KB of LDS the table entries can be the records' byte addresses
-  // (PATH 3: one shift less per point in the score loop); NDTPSO_BYTE_ENTRIES=0 keeps the general form
-  static const bool allow_byte_entries = [] {
-    const char* e = std::getenv("NDTPSO_BYTE_ENTRIES");
-    return !(e && e[0] == '0');
-  }();
-  const bool byte_entries = plan.path == 2 && allow_byte_entries && t_plan_force.byte_entries != 0 &&
-                            plan.dn.rec_off + dense_rec_bytes(wn.rec_cap + 1) <= 65536;
-  if (d_ximg) {  // exact mode on the dense form
-    if (byte_entries) LAUNCH_PAIRS_X(3); else LAUNCH_PAIRS_X(2);
-  } else if (mode == NDTPSO_SCORE_F32) {
-    if (byte_entries) LAUNCH_PAIRS(kScoreF32, 3); else if (plan.path == 2) LAUNCH_PAIRS(kScoreF32, 2); else if (plan.path == 1) LAUNCH_PAIRS(kScoreF32, 1); else LAUNCH_PAIRS(kScoreF32, 0);
-  } else {
-    if (plan.path == 9) { if (plan.boxy) LAUNCH_PAIRS_CANSB(kScoreF64, 9, false, false, false, 2, true); else LAUNCH_PAIRS_CANSB(kScoreF64, 9, false, false, false, 2, false); }
-    else if (plan.path == 8) { if (plan.boxy) LAUNCH_PAIRS_CANSB(kScoreF64, 8, false, false, false, 2, true); else LAUNCH_PAIRS_CANSB(kScoreF64, 8, false, false, false, 2, false); }
-    else if (plan.path == 1) LAUNCH_PAIRS(kScoreF64, 1); else LAUNCH_PAIRS(kScoreF64, 0);
-  }
-#undef LAUNCH_PAIRS
-#undef LAUNCH_PAIRS_X
-#undef LAUNCH_PAIRS_C
-#undef LAUNCH_PAIRS_CA
-#undef LAUNCH_PAIRS_CAN
-#undef LAUNCH_PAIRS_CANS
-#undef LAUNCH_PAIRS_CANSB
-  HIP_TRY(c, hipGetLastError());
-  return NDTPSO_OK;
-}
-
-static int align_pairs_dev_on_stream(ndtpso_ctx* c, uint32_t n_pairs, const float* d_ref, const float* d_new,
-                                     const ndtpso_scan_geom* geom, const ndtpso_grid* grid, const double* d_guess,
-                                     const double* d_dev, const ndtpso_pso_config* cfg, const uint32_t* d_seeds,
-                                     const int32_t* d_tables, int mode, double* d_pose, double* d_cost,
-                                     ndtpso_align_stats* d_stats);
-
-int ndtpso_align_pairs_dev(ndtpso_ctx* c, uint32_t n_pairs, const float* d_ref, const float* d_new,
-                           const ndtpso_scan_geom* geom, const ndtpso_grid* grid, const double* d_guess,
-                           const double* d_dev, const ndtpso_pso_config* cfg, const uint32_t* d_seeds,
-                           const int32_t* d_tables, int mode, double* d_pose, double* d_cost,
-                           ndtpso_align_stats* d_stats) {
-  if (!c) return NDTPSO_E_ARG;
-  if (int rc = exact_mode_resolve(c, &mode)) return rc;
-  // one batch at a time (the default), or a batch too small to fill the device (those run as clusters of workgroups
-  // with per-context counters): on the context's stream, behind whatever is still in flight
-  if (c->pipe_depth < 2 || n_pairs * 2u <= (uint32_t)c->n_cus) {
-    if (c->pipe_depth > 1)
-      if (int rc = ndtpso_pipeline_flush(c, 0)) return rc;
-    return align_pairs_dev_on_stream(c, n_pairs, d_ref, d_new, geom, grid, d_guess, d_dev, cfg, d_seeds, d_tables, mode,
-                                     d_pose, d_cost, d_stats);
-  }
-  HIP_TRY(c, hipSetDevice(c->device));
-  ndtpso_ctx::PipeLane& lane = c->lanes[c->pipe_calls % (unsigned)c->pipe_depth];
-  // the lane's previous call is ordered before this one by the lane's stream; the inputs by an event of the caller's
-  HIP_TRY(c, hipEventRecord(c->pipe_in, c->stream));
-  HIP_TRY(c, hipStreamWaitEvent(lane.stream, c->pipe_in, 0));
-  hipStream_t caller = c->stream;
-  c->stream = lane.stream;
-  std::swap(c->ws, lane.ws);
-  std::swap(c->gate, lane.gate);
-  std::swap(c->ximg, lane.ximg);
-  const int rc = align_pairs_dev_on_stream(c, n_pairs, d_ref, d_new, geom, grid, d_guess, d_dev, cfg, d_seeds, d_tables,
-                                           mode, d_pose, d_cost, d_stats);
-  std::swap(c->ws, lane.ws);
-  std::swap(c->gate, lane.gate);
-  std::swap(c->ximg, lane.ximg);
-  c->stream = caller;
-  if (rc != NDTPSO_OK) return rc;
-  HIP_TRY(c, hipEventRecord(lane.done, lane.stream));
-  lane.pending = true;
-  lane.ticket = c->pipe_calls++;
-  return NDTPSO_OK;
-}
-
-static int align_pairs_dev_on_stream(ndtpso_ctx* c, uint32_t n_pairs, const float* d_ref, const float* d_new,
-                                     const ndtpso_scan_geom* geom, const ndtpso_grid* grid, const double* d_guess,
-                                     const double* d_dev, const ndtpso_pso_config* cfg, const uint32_t* d_seeds,
-                                     const int32_t* d_tables, int mode, double* d_pose, double* d_cost,
-                                     ndtpso_align_stats* d_stats) {
-  if (!c || !d_ref || !d_new || !d_guess || !d_dev || !d_pose || (!d_seeds && !d_tables))
-    return fail(c, NDTPSO_E_ARG, "null argument");
-  if (mode != NDTPSO_SCORE_F32 && mode != NDTPSO_SCORE_F64 && mode != NDTPSO_SCORE_EXACT) return fail(c, NDTPSO_E_ARG, "bad score mode");
-  if (n_pairs == 0) return NDTPSO_OK;
-  HIP_TRY(c, hipSetDevice(c->device));
-  AlignStats* st = reinterpret_cast<AlignStats*>(d_stats);
-  if (!st) {  // the fp32 pass reports underflowed alignments through the stats block: keep one internally
-    HIP_TRY(c, c->gate.reserve(sizeof(AlignStats) * (size_t)n_pairs));
-    st = reinterpret_cast<AlignStats*>(c->gate.p);
-  }
-  int path = 0;
-  const bool small_batch = n_pairs * 2u <= (uint32_t)c->n_cus;
-  HIP_TRY(c, hipMemsetAsync(st, 0, sizeof(AlignStats) * (size_t)n_pairs, c->stream));
-  // exact mode: the fp32-score kernel arbitrating in fp64 (dense form) -- or, where the dense form is not available,
-  // the fp64 score itself; flagged alignments are redone by the fp64-score kernel
-  bool exact = mode == NDTPSO_SCORE_EXACT;
-  if (exact) {
-    GridP g0;
-    WinP w0;
-    Plan p0;
-    int waves0 = 0;
-    const int rc0 = pairs_plan(geom, grid, cfg, NDTPSO_SCORE_F32, n_pairs, &g0, &w0, &p0, &waves0, true, (unsigned)c->n_cus, true);
-    mode = (rc0 == NDTPSO_OK && p0.path == 2) ? NDTPSO_SCORE_F32 : NDTPSO_SCORE_F64;
-    exact = mode == NDTPSO_SCORE_F32;
-  }
-  bool shrunk = false;
-  // (what the previous call of this configuration reported: see ndtpso_ctx::pairs_fb)
-  if (!c->pairs_fb) {
-    HIP_TRY(c, hipHostMalloc((void**)&c->pairs_fb, 64, hipHostMallocMapped | hipHostMallocCoherent));
-    std::memset(c->pairs_fb, 0, 64);
-  }
-  uint32_t last_overflow = 0;  // pairs of the previous call (same configuration) whose box outgrew the two-per-CU table
-  {
-    uint64_t key = 1469598103934665603ull;
-    const uint64_t key_before = c->fb_key;
-    auto mix = [&key](uint64_t v) { key = (key ^ v) * 1099511628211ull; };
-    mix(geom->n_beams), mix((uint64_t)(geom->max_range * 1024.f)), mix(grid->width), mix(grid->height), mix((uint64_t)(grid->cell_side * 65536.));
-    mix((uint64_t)cfg->population), mix((uint64_t)mode), mix(exact ? 1 : 0);
-    const uint32_t now = __atomic_load_n(c->pairs_fb, __ATOMIC_RELAXED);
-    // (the gated largest-table launch below is issued only where tables have overflowed lately -- or nothing is known yet:
-    // a batch of 512 workgroups that all leave at once still costs the device 4 us, and the benchmark's shape never needs it.
-    // An overflow that comes as a surprise is still served, by the slower launches further down, and switches it on.)
-    c->fb_overflowed = key != c->fb_key || now != c->fb_seen || c->fb_overflowed_calls > 0;
-    if (key == c->fb_key && now != c->fb_seen) c->fb_overflowed_calls = 16;  // keep it on for the next calls
-    else if (c->fb_overflowed_calls > 0) --c->fb_overflowed_calls;
-    if (key != c->fb_key) {
-      c->fb_key = key;
-      c->fb_big_first = false;
-      c->fb_big_calls = 0;
-      c->fb_overflowed_calls = 1;
-    } else if (!c->fb_big_first && c->fb_last_pairs && (uint64_t)(now - c->fb_seen) * 4u > c->fb_last_pairs) {
-      c->fb_big_first = true;
-      static const bool log_plan = std::getenv("NDTPSO_LOG_PLAN") != nullptr;  // diagnostics
-      if (log_plan)
-        std::fprintf(stderr, "ndtpso: %u of the last call's %u pairs outgrew the two-per-CU cell table: largest table first from now on\n",
-                     now - c->fb_seen, c->fb_last_pairs);
-    }
-    // ... and not for ever: one burst of large rooms must not pin the configuration to one workgroup per compute unit for the
-    // life of the context -- every 64 calls the two-per-CU table is tried again (and, if a quarter of the pairs still
-    // outgrows it, the next call is back to the largest table)
-    if (c->fb_big_first && ++c->fb_big_calls >= 64) {
-      c->fb_big_first = false;
-      c->fb_big_calls = 0;
-    }
-    last_overflow = (key == key_before) ? now - c->fb_seen : 0u;
-    c->fb_seen = now;
-    c->fb_last_pairs = n_pairs;
-  }
-  const bool big_first = c->fb_big_first && !small_batch;
-  int rc = launch_pairs(c, n_pairs, d_ref, d_new, geom, grid, d_guess, d_dev, cfg, d_seeds, d_tables, mode, d_pose, d_cost,
-                        st, 0u, true, &path, small_batch, exact, big_first, &shrunk, big_first ? nullptr : c->pairs_fb);
-  if (big_first) shrunk = false;  // (nothing larger to fall back to)
-  if (rc != NDTPSO_OK) return rc;
-  if (no_redo_requested()) return rc;  // diagnostics only
-  // A FEW flagged pairs in a batch that fills the device (1081 beams at 0.25 m: 7 rooms of 512 outgrow the table): on one
-  // workgroup each, behind the main launch, they took as long again as the whole batch (fp64 score: 2.8 ms after 5.1 ms).  They
-  // run as CLUSTERS instead -- the fp64 score on K workgroups per pair, as a batch too small for the device does -- through a
-  // list a one-wave kernel makes of them: 0.9 ms.  Tried only where the previous calls of the configuration saw flagged pairs
-  // (the list's own count, the striding redo's count, the main launch's overflow count: pinned words), for up to 32 of them,
-  // with one batch at a time in the context (two in flight: the other lane's workgroups hold the compute units a cluster needs
-  // together).  Whatever it does not serve -- pairs beyond the list, a cluster that gave up -- keeps its flags and goes through
-  // the gated launches below as before.  Results: the fp64 score's, whichever form computes them.  NDTPSO_REDO_CLUSTERS=0: off.
-  const char* redo_env = std::getenv("NDTPSO_REDO_CLUSTERS");
-  if (!(redo_env && redo_env[0] == '0') && !small_batch && c->pipe_depth < 2 && (exact || mode == NDTPSO_SCORE_F64)) {
-    const uint32_t mask = exact ? (kStatusNeedsF64 | kStatusNeedsBitmap) : kStatusNeedsBitmap;
-    uint32_t* seen_w = c->pairs_fb + 8 + (exact ? 1 : 0);
-    const uint32_t seen = std::max(std::max(__atomic_load_n(seen_w, __ATOMIC_RELAXED), __atomic_load_n(c->pairs_fb + 7, __ATOMIC_RELAXED)),
-                                   (path == 2 || path >= 8) ? last_overflow : 0u);
-    if (seen >= 1u && seen <= 32u) {
-      const uint32_t cap = std::min<uint32_t>(n_pairs, std::max<uint32_t>(8u, 2u * seen));
-      HIP_TRY(c, c->redo_list.reserve((size_t)(1u + 64u) * sizeof(uint32_t)));
-      uint32_t* list = (uint32_t*)c->redo_list.p;
-      hipLaunchKernelGGL(k_redo_list, dim3(1), dim3(kWave), 0, c->stream, (const AlignStats*)st, n_pairs, mask, list, cap, seen_w);
-      HIP_TRY(c, hipGetLastError());
-      rc = launch_pairs(c, n_pairs, d_ref, d_new, geom, grid, d_guess, d_dev, cfg, d_seeds, d_tables, NDTPSO_SCORE_F64, d_pose, d_cost,
-                        st, 0u, true, nullptr, true, false, false, nullptr, nullptr, list, cap, mask);
-      if (rc != NDTPSO_OK && rc != NDTPSO_E_STATE) return rc;
-      if (rc == NDTPSO_OK) g_redo_cluster_launches.fetch_add(1, std::memory_order_relaxed);
-      rc = NDTPSO_OK;
-    }
-  }
-  // Gated redo launches (every workgroup whose alignment is not flagged exits on its first instruction).  First of all: the
-  // dense forms size their cell table so that two workgroups share a compute unit; an alignment whose box -- scan A's
-  // occupied cells -- outgrew that table gets the same kernel again with the largest table a workgroup can hold (0.25 m cells,
-  // a room seen at an angle: 7 of 512 pairs; 1441 beams at 0.3 m: 370 of 512), before anything slower is considered
-  if (shrunk && c->fb_overflowed && (path == 2 || path >= 8) && !small_batch) {
-    rc = launch_pairs(c, n_pairs, d_ref, d_new, geom, grid, d_guess, d_dev, cfg, d_seeds, d_tables, mode, d_pose, d_cost,
-                      st, kStatusNeedsBitmap, true, nullptr, false, exact, true);
-    if (rc != NDTPSO_OK && rc != NDTPSO_E_CAPACITY) return rc;
-  }
-  int path_redo = 0;
-  if (small_batch) {  // a cluster that was not co-resident gave up (bounded wait): those alignments on one workgroup each
-    // (on one workgroup the fp64 score may take its dense form -- a cluster keeps the bitmap form --, which hands an alignment
-    // whose box outgrows its table on to the bitmap form: the gated launch below must then be issued for THIS launch's path too)
-    rc = launch_pairs(c, n_pairs, d_ref, d_new, geom, grid, d_guess, d_dev, cfg, d_seeds, d_tables, mode, d_pose, d_cost,
-                      st, kStatusClusterTimeout, true, &path_redo, false, exact);
-    if (rc != NDTPSO_OK) return rc;
-  }
-  if (mode != NDTPSO_SCORE_F32) {
-    // fp64 score on the dense table (path 8 / 9): an occupied box that outgrew the provisioned table, or a table holding a
-    // cell whose exponents the spelt-out exponential must not be trusted with -> the bitmap form, gated
-    if (path >= 8 || path_redo >= 8) {
-      rc = launch_pairs(c, n_pairs, d_ref, d_new, geom, grid, d_guess, d_dev, cfg, d_seeds, d_tables, NDTPSO_SCORE_F64, d_pose,
-                        d_cost, st, kStatusNeedsBitmap, false, nullptr);
-      if (rc == NDTPSO_E_CAPACITY) rc = NDTPSO_OK;
-    }
-    return rc;
-  }
-  // Gated redo launches (every workgroup whose alignment is not flagged exits on its first instruction):
-  //  - dense form only: alignments whose occupied box exceeded the provisioned cell table -> bitmap form;
-  //  - alignments whose fp32 costs fell in the underflow regime (degenerate overlap) -> fp64 score.
-  // If a redo form does not fit in LDS its flag simply stays set in the stats block.
-  // (exact mode: the bitmap form cannot arbitrate, so both kinds of flagged alignment go to the fp64-score kernel, in one launch)
-  if (path == 2 && !exact) {
-    rc = launch_pairs(c, n_pairs, d_ref, d_new, geom, grid, d_guess, d_dev, cfg, d_seeds, d_tables, NDTPSO_SCORE_F32, d_pose,
-                      d_cost, st, kStatusNeedsBitmap, false, nullptr);
-    if (rc != NDTPSO_OK && rc != NDTPSO_E_CAPACITY) return rc;
-  }
-  // (the fp64 score's dense form first -- it sets kStatusNeedsBitmap itself where it cannot run --, the bitmap form for what is left)
-  int path64 = 0;
-  rc = launch_pairs(c, n_pairs, d_ref, d_new, geom, grid, d_guess, d_dev, cfg, d_seeds, d_tables, NDTPSO_SCORE_F64, d_pose,
-                    d_cost, st, exact ? (kStatusNeedsF64 | kStatusNeedsBitmap) : kStatusNeedsF64, true, &path64);
-  if (rc != NDTPSO_OK && rc != NDTPSO_E_CAPACITY) return rc;
-  if (path64 >= 8) {
-    rc = launch_pairs(c, n_pairs, d_ref, d_new, geom, grid, d_guess, d_dev, cfg, d_seeds, d_tables, NDTPSO_SCORE_F64, d_pose,
-                      d_cost, st, kStatusNeedsBitmap, false, nullptr);
-  }
-  return rc == NDTPSO_E_CAPACITY ? NDTPSO_OK : rc;
-}
-
-// What the fused kernels could not serve -- an occupied box beyond the largest table a workgroup holds whose bitmap form does
-// not fit LDS either (cells of 0.125 m in a 60 m frame: a dozen pairs in 600) -- comes back flagged.  An entry that has the
-// inputs on the host and has just synchronised (ndtpso_align_pairs, ndtpso_align_pairs_sharded) sends those pairs, one by one,
-// through the RESIDENT frame (ndtpso_map_*: scan A inserted into a frame in HBM and built there, the alignment reading the
-// packed table from its HBM image where LDS cannot hold it), whose results are the fused kernels' bit for bit.  One frame per
-// call, cleared between pairs; nothing of this is allocated unless a pair needs it.  A frame the resident path cannot hold
-// either -- a million cells -- leaves its pairs flagged, as the kernels did: the other pairs' results stand.
-// (The asynchronous entries on device buffers leave the flag to their caller: NDTPSO_STATUS_FLAGS.)
-static int resolve_flagged_pairs(ndtpso_ctx* c, size_t B, const float* ref_ranges, const float* new_ranges, const ndtpso_scan_geom* geom,
-                                 const ndtpso_grid* grid, const double* guess, const double* deviation, const ndtpso_pso_config* cfg,
-                                 const uint32_t* seeds, const int32_t* rand_tables, int mode, double* out_pose, double* out_cost,
-                                 AlignStats* hs) {
-  const size_t nb = geom->n_beams, n_draw = ndtpso_rand_draws(cfg);
-  if (no_redo_requested()) return NDTPSO_OK;  // (diagnostics: what the main launch alone left flagged)
-  ndtpso_map* fb_map = nullptr;
-  ndtpso_points *fb_a = nullptr, *fb_b = nullptr;
-  int fb_rc = NDTPSO_OK;
-  for (size_t b = 0; b < B && fb_rc == NDTPSO_OK; ++b) {
-    if (!(hs[b].status & (kStatusNeedsBitmap | kStatusNeedsF64 | kStatusClusterTimeout))) continue;
-    const double zero3[3] = {0., 0., 0.};
-    if (!fb_map) {
-      fb_rc = ndtpso_map_create(c, grid, 0., (uint64_t)std::max<size_t>(nb, 4096) * 16 * 64, &fb_map);
-      if (fb_rc == NDTPSO_OK) fb_rc = ndtpso_points_create(c, (uint32_t)nb, &fb_a);
-      if (fb_rc == NDTPSO_OK) fb_rc = ndtpso_points_create(c, (uint32_t)nb, &fb_b);
-    } else {
-      fb_rc = ndtpso_map_clear(fb_map);
-    }
-    // reference frame <- scan A at identity; the frame being matched is a one-cell frame of the same size, its list the points
-    // inside it (ndtpso_slam_node.cpp:229-230: `clip`)
-    if (fb_rc == NDTPSO_OK) fb_rc = ndtpso_points_load_scan(fb_a, ref_ranges + b * nb, geom, zero3, grid, 0);
-    if (fb_rc == NDTPSO_OK) fb_rc = ndtpso_map_insert(fb_map, fb_a, nullptr);
-    if (fb_rc == NDTPSO_OK) fb_rc = ndtpso_map_build(fb_map);
-    if (fb_rc == NDTPSO_OK) fb_rc = ndtpso_points_load_scan(fb_b, new_ranges + b * nb, geom, zero3, grid, 0);
-    double pose[3] = {0., 0., 0.}, cost = 0.;
-    ndtpso_align_stats st1;
-    if (fb_rc == NDTPSO_OK)
-      fb_rc = ndtpso_map_align(fb_map, fb_b, guess + 3 * b, deviation + 3 * b, cfg, seeds ? seeds[b] : 0u,
-                               rand_tables ? rand_tables + b * n_draw : nullptr, mode, pose, &cost, &st1);
-    if (fb_rc != NDTPSO_OK) break;
-    std::memcpy(out_pose + 3 * b, pose, sizeof(pose));
-    if (out_cost) out_cost[b] = cost;
-    std::memcpy(&hs[b], &st1, sizeof(AlignStats));
-  }
-  if (fb_a) ndtpso_points_destroy(fb_a);
-  if (fb_b) ndtpso_points_destroy(fb_b);
-  if (fb_map) ndtpso_map_destroy(fb_map);
-  return (fb_rc != NDTPSO_OK && fb_rc != NDTPSO_E_CAPACITY) ? fb_rc : NDTPSO_OK;
-}
-
-int ndtpso_align_pairs(ndtpso_ctx* c, uint32_t n_pairs, const float* ref_ranges, const float* new_ranges,
-                       const ndtpso_scan_geom* geom, const ndtpso_grid* grid, const double* guess,
-                       const double* deviation, const ndtpso_pso_config* cfg, const uint32_t* seeds,
-                       const int32_t* rand_tables, int mode, double* out_pose, double* out_cost,
-                       ndtpso_align_stats* stats) {
-  if (!c || !ref_ranges || !new_ranges || !geom || !guess || !deviation || !out_pose || (!seeds && !rand_tables))
-    return fail(c, NDTPSO_E_ARG, "null argument");
-  if (int rc = check_pso(c, cfg)) return rc;
-  if (n_pairs == 0) return NDTPSO_OK;
-  if (int rc = exact_mode_resolve(c, &mode)) return rc;  // (before anything is staged in the context's buffers)
-  HIP_TRY(c, hipSetDevice(c->device));
-  const size_t B = n_pairs, nb = geom->n_beams, n_draw = ndtpso_rand_draws(cfg);
-  HIP_TRY(c, c->ranges.reserve(B * nb * 4));
-  HIP_TRY(c, c->ranges2.reserve(B * nb * 4));
-  HIP_TRY(c, c->poses.reserve(B * 48));
-  HIP_TRY(c, c->out.reserve(B * (32 + sizeof(AlignStats))));
-  HIP_TRY(c, c->seeds.reserve(B * 4));
-  if (rand_tables) HIP_TRY(c, c->table.reserve(B * n_draw * 4));
-  HIP_TRY(c, hipMemcpyAsync(c->ranges.p, ref_ranges, B * nb * 4, hipMemcpyHostToDevice, c->stream));
-  HIP_TRY(c, hipMemcpyAsync(c->ranges2.p, new_ranges, B * nb * 4, hipMemcpyHostToDevice, c->stream));
-  double* d_guess = (double*)c->poses.p;
-  double* d_dev = d_guess + 3 * B;
-  HIP_TRY(c, hipMemcpyAsync(d_guess, guess, B * 24, hipMemcpyHostToDevice, c->stream));
-  HIP_TRY(c, hipMemcpyAsync(d_dev, deviation, B * 24, hipMemcpyHostToDevice, c->stream));
-  if (seeds) HIP_TRY(c, hipMemcpyAsync(c->seeds.p, seeds, B * 4, hipMemcpyHostToDevice, c->stream));
-  if (rand_tables) HIP_TRY(c, hipMemcpyAsync(c->table.p, rand_tables, B * n_draw * 4, hipMemcpyHostToDevice, c->stream));
-  double* d_pose = (double*)c->out.p;
-  double* d_cost = d_pose + 3 * B;
-  ndtpso_align_stats* d_stats = reinterpret_cast<ndtpso_align_stats*>(d_cost + B);
-  HIP_TRY(c, hipMemsetAsync(c->out.p, 0, B * (32 + sizeof(AlignStats)), c->stream));
-  const int rc = ndtpso_align_pairs_dev(c, n_pairs, (const float*)c->ranges.p, (const float*)c->ranges2.p, geom, grid,
-                                        d_guess, d_dev, cfg, seeds ? (const uint32_t*)c->seeds.p : nullptr,
-                                        rand_tables ? (const int32_t*)c->table.p : nullptr, mode, d_pose, d_cost,
-                                        d_stats);
-  if (rc != NDTPSO_OK) return rc;
-  // with batches in flight (ndtpso_set_pipeline_depth) the launch went to a lane's stream: the copies below and the
-  // next call's uploads into the same staging buffers must come behind it
-  if (int frc = ndtpso_pipeline_flush(c, 0)) return frc;
-  HIP_TRY(c, hipMemcpyAsync(out_pose, d_pose, B * 24, hipMemcpyDeviceToHost, c->stream));
-  if (out_cost) HIP_TRY(c, hipMemcpyAsync(out_cost, d_cost, B * 8, hipMemcpyDeviceToHost, c->stream));
-  std::vector<AlignStats> own_stats;
-  AlignStats* hs = reinterpret_cast<AlignStats*>(stats);
-  if (!hs) {
-    own_stats.resize(B);
-    hs = own_stats.data();
-  }
-  HIP_TRY(c, hipMemcpyAsync(hs, d_stats, B * sizeof(AlignStats), hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(c, hipStreamSynchronize(c->stream));
-  if (int rc = resolve_flagged_pairs(c, B, ref_ranges, new_ranges, geom, grid, guess, deviation, cfg, seeds, rand_tables, mode, out_pose,
-                                     out_cost, hs))
-    return rc;
-  return NDTPSO_OK;
-}
+#include "ndtpso_pairs.inc"
 
 #ifdef NDTPSO_VERIFY_MARGIN
 // diagnostic builds only (tests/test_gpu_margin.py): per alignment of the fused-pairs launches since the last reset, kVerifyRow (24) doubles

@@ -819,7 +819,7 @@ int ndtpso_map_align(ndtpso_map* m, const ndtpso_points* pts, const double guess
   if (!m || !pts) return NDTPSO_E_ARG;
   ndtpso_ctx* c = m->ctx;
   if (!guess || !deviation || !out_pose) return fail(c, NDTPSO_E_ARG, "null argument");
-  if (mode != NDTPSO_SCORE_F32 && mode != NDTPSO_SCORE_F64 && mode != NDTPSO_SCORE_EXACT) return fail(c, NDTPSO_E_ARG, "bad score mode");
+  if (int rc = check_mode(c, mode)) return rc;
   if (int rc = check_pso(c, cfg)) return rc;
   if (int rc = exact_mode_resolve(c, &mode)) return rc;
   c->clk_enter = std::chrono::steady_clock::now();
@@ -848,10 +848,13 @@ int ndtpso_map_align(ndtpso_map* m, const ndtpso_points* pts, const double guess
   bool late_done = false;  // the late path ran: speculation committed, header with the host
   AlignSrc src{(const unsigned char*)m->image.p, m->p.g, WinP{}, (const double2*)pts->xy.p,
                std::max<uint32_t>(pts->n_upper, 1u), (const uint32_t*)pts->n_dev.p, out_cost != nullptr};
-  Plan probe;
-  if (map_late_bound(m, mode, &src.wn) &&
-      make_plan(NDTPSO_SCORE_F32, src.g, src.wn, (int)src.n, cfg->population, &probe, false, true, true, mode == NDTPSO_SCORE_EXACT) &&
-      probe.path == 2) {
+  // (the probe only asks whether align_once will find the dense form for the upper bound: map_late_bound refuses the fp64 score)
+  bool late = map_late_bound(m, mode, &src.wn);
+  if (late) {
+    const ScorePlan probe = resolve_score_plan(mode, src.g, src.wn, (int)src.n, cfg->population, prebuilt_table_ask());
+    late = probe.ok && probe.plan.path == 2;
+  }
+  if (late) {
     src.late_hdr = reinterpret_cast<const uint32_t*>(m->hdr.p);
     double host[kResultDoubles];
     const AfterLaunch og{&map_commit_speculation_cb, m};
@@ -891,8 +894,8 @@ int ndtpso_map_cost(ndtpso_map* m, ndtpso_points* pts, const double* poses, uint
   if (!m || !pts) return NDTPSO_E_ARG;
   ndtpso_ctx* c = m->ctx;
   if (!poses || !costs || n_poses == 0) return fail(c, NDTPSO_E_ARG, "null argument");
+  if (int rc = check_mode(c, mode)) return rc;
   if (mode == NDTPSO_SCORE_EXACT) mode = NDTPSO_SCORE_F64;  // a single cost: the exact mode is the fp64 score
-  if (mode != NDTPSO_SCORE_F32 && mode != NDTPSO_SCORE_F64) return fail(c, NDTPSO_E_ARG, "bad score mode");
   HIP_TRY(c, hipSetDevice(c->device));
   if (m->spec) {
     if (int rc = map_commit_speculation(m)) return rc;

@@ -33,16 +33,13 @@ struct BatchGroup {   // the jobs of one launch: one kernel instantiation
 
 // which job kernel, if any, runs an alignment of `mode` against a table of window `wn`: -1 none (the single path)
 static int batch_plan_job(int mode, const GridP& g, const WinP& wn, uint32_t n, const ndtpso_pso_config* cfg, Plan* plan) {
-  const int n_max = std::max<int>((int)n, 1);
-  if (mode == NDTPSO_SCORE_EXACT || mode == NDTPSO_SCORE_F32) {
-    const bool exact = mode == NDTPSO_SCORE_EXACT;
-    if (make_plan(NDTPSO_SCORE_F32, g, wn, n_max, cfg->population, plan, false, true, true, exact) && plan->path == 2)
-      return plan->L.swarm_global ? -1 : (exact ? 1 : 0);
-    if (!exact) return -1;  // (bitmap forms, the table image in HBM)
-  }
-  // the fp64 score (asked for, or the exact mode where the table does not take the dense form: align_once)
-  if (!make_plan(NDTPSO_SCORE_F64, g, wn, n_max, cfg->population, plan, false, true, true, false)) return -1;
-  return (plan->path == 1 && !plan->L.swarm_global) ? 2 : -1;
+  const ScorePlan resolved = resolve_score_plan(mode, g, wn, std::max<int>((int)n, 1), cfg->population, prebuilt_table_ask());  // (as align_once)
+  *plan = resolved.plan;
+  // the job kernels exist for the swarm in LDS, and for two table forms: the fp32 score's dense form (the other forms, the table
+  // image in HBM: the single path) and the fp64 score's bitmap form on cells of a power of two
+  if (!resolved.ok || plan->L.swarm_global) return -1;
+  if (resolved.mode == NDTPSO_SCORE_F32) return plan->path == 2 ? (resolved.arbitrates ? 1 : 0) : -1;
+  return plan->path == 1 ? 2 : -1;
 }
 
 static void batch_launch_kernel(ndtpso_ctx* c, const BatchGroup& gr, const AlignJob* d_jobs, int table_vec) {
@@ -68,7 +65,7 @@ extern "C" int ndtpso_map_align_batch(ndtpso_ctx* c, ndtpso_map_align_job* jobs,
     if (!jobs[i].map || !jobs[i].new_points) return fail(c, NDTPSO_E_ARG, "null argument");
     if (jobs[i].map->ctx != c || jobs[i].new_points->ctx != c) return fail(c, NDTPSO_E_ARG, "a map or scan of another context");
   }
-  if (mode != NDTPSO_SCORE_F32 && mode != NDTPSO_SCORE_F64 && mode != NDTPSO_SCORE_EXACT) return fail(c, NDTPSO_E_ARG, "bad score mode");
+  if (int rc = check_mode(c, mode)) return rc;
   if (int rc = check_pso(c, cfg)) return rc;
   for (uint32_t i = 0; i < n_jobs; ++i) {
     ndtpso_map_align_job& j = jobs[i];
