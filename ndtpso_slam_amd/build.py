@@ -107,8 +107,12 @@ def build_hip(force: bool = False, verbose: bool = False) -> str:
 #   why     -DNDTPSO_WHY_BITS       status bits that say why an alignment was handed to the fp64-score kernel (scripts/shape_diag.py)
 #   broken  -DNDTPSO_BREAK_ARBITRATION  the arbitration's unit form returns scores that are off by 2^-44: what the start-up check
 #                                   of the exact mode exists to catch (tests/test_gpu_exact_check.py loads it in a subprocess)
+#   noquick -DNDTPSO_QUICK_DECIDE=0 -DNDTPSO_EARLY_STOP=0  every evaluation through the fp64 lane reduce, as before the quick
+#                                   decision: the other side of tests/test_gpu_quick_decide.py and of the A/B
+#   quickcount -DNDTPSO_COUNT_QUICK  `gbest_updates` reports the evaluations decided quickly (against `cost_evals`)
 VARIANTS = {"budget": ["-DNDTPSO_PHASE_BUDGET"], "verify": ["-DNDTPSO_VERIFY_MARGIN"], "broken": ["-DNDTPSO_BREAK_ARBITRATION"],
-            "why": ["-DNDTPSO_WHY_BITS"]}
+            "why": ["-DNDTPSO_WHY_BITS"], "noquick": ["-DNDTPSO_QUICK_DECIDE=0", "-DNDTPSO_EARLY_STOP=0"],
+            "quickcount": ["-DNDTPSO_COUNT_QUICK"]}
 
 
 def variant_path(name: str) -> str:

@@ -331,6 +331,60 @@ __device__ __forceinline__ double wave_sum(double v) {
   return readlane_f64(v, 63);
 }
 
+// ---- the quick decision (NDTPSO_QUICK_DECIDE) -------------------------------------------------------------------------
+// Nine evaluations in ten lose against their pbest and the gbest by tens of score units; a sum good to 1e-3 says so, and
+// the fp64 reduce above (two moves and an fp64 add per level) is then work the result does not need.  wave_sum_f32 is the
+// same six-level tree on the lane sums rounded to fp32, the DPP controls on the add itself: seven instructions, result
+// uniform.  How far it can lie from the exact sum S of the 64 fp64 lane accumulators L_i (each a sum of terms in [0, 1],
+// so L_i >= 0 and S <= n, the padding being masked or null): one rounding per lane for the conversion, one per level of
+// the tree, each relative 2^-24 = u on a partial sum of non-negative numbers -- |s32 - S| <= ((1 + u)^7 - 1) S.  wave_sum
+// itself rounds six times in fp64, 6 * 2^-53 S.  quick_eps(n) = 8 u n covers both with the second-order terms.
+// 0: today's text -- every evaluation goes through wave_sum.  Off as well wherever the exact value is looked at
+// evaluation by evaluation (NDTPSO_VERIFY_MARGIN).
+#ifndef NDTPSO_QUICK_DECIDE
+#define NDTPSO_QUICK_DECIDE 1
+#endif
+#ifdef NDTPSO_VERIFY_MARGIN
+constexpr bool kQuickDecide = false;
+#else
+constexpr bool kQuickDecide = NDTPSO_QUICK_DECIDE != 0;
+#endif
+__device__ __forceinline__ double quick_eps(int n_points) { return 0x1p-21 * (double)n_points; }
+// s_waitcnt vmcnt(0), in front of the evaluation loops.  The proposal step reads its draws through a generic pointer (LDS
+// or HBM: a flat load), and as long as the compiler's bookkeeping holds a flat access whose vmcnt it has not seen waited
+// for, every wait for an LDS result in the code behind it is lgkmcnt(0) -- the trips' LDS reads, issued six and twelve at
+// a time and consumed one by one as they arrive (lgkmcnt(5), (4), ...), were then waited for all at once.  The loop's
+// former text had a spill reload, with its vmcnt(0), in front of it by luck; with the quick decision beside the loop the
+// reload went, the kernel lost every graded wait of its evaluation loop (417 -> 284 in the benchmark's kernel) and 3.7 %
+// of its speed although it issued 3.8 % fewer VALU instructions.  Nothing is in flight there that this waits long for.
+__device__ __forceinline__ void settle_vmem() { __builtin_amdgcn_s_waitcnt(0x0F70); }  // vmcnt(0), expcnt and lgkmcnt left alone
+// LEVELS 6: all 64 lanes, the sum in lane 63 (returned, uniform).  5: the two halves of the wave apart (eval_pair_half),
+// the sums in lanes 31 and 63 (returned per lane, meaningful in those two).
+// (one block: the wait states between a VALU write and a DPP read of the same register are spelt out, the compiler does not
+// look into the text; the first covers the conversion in front of it)
+template <int LEVELS = 6>
+__device__ __forceinline__ float wave_sum_f32(float v) {
+  static_assert(LEVELS == 5 || LEVELS == 6, "whole wave or its halves");
+  asm("s_nop 1\n\t"
+      "v_add_f32_dpp %0, %0, %0 quad_perm:[1,0,3,2] row_mask:0xf bank_mask:0xf\n\t"
+      "s_nop 1\n\t"
+      "v_add_f32_dpp %0, %0, %0 quad_perm:[2,3,0,1] row_mask:0xf bank_mask:0xf\n\t"
+      "s_nop 1\n\t"
+      "v_add_f32_dpp %0, %0, %0 row_half_mirror row_mask:0xf bank_mask:0xf\n\t"
+      "s_nop 1\n\t"
+      "v_add_f32_dpp %0, %0, %0 row_mirror row_mask:0xf bank_mask:0xf\n\t"
+      "s_nop 1\n\t"
+      "v_add_f32_dpp %0, %0, %0 row_bcast:15 row_mask:0xa bank_mask:0xf"  // rows 1 and 3 += lane 15 of the row below
+      : "+v"(v));
+  if constexpr (LEVELS == 6) {
+    asm("s_nop 1\n\t"
+        "v_add_f32_dpp %0, %0, %0 row_bcast:31 row_mask:0xc bank_mask:0xf"  // rows 2 and 3 += lane 31
+        : "+v"(v));
+    return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), 63));
+  }
+  return v;
+}
+
 // cell coordinates of an in-frame point, following NDTFrame::getCellIndex (ndtframe.cpp:240-249):
 // floor((x + width/2.)/cell_side), floor((y + height/2.)/cell_side).  x + hw > 0 inside the
 // strict bounds, so truncation equals floor.
@@ -763,7 +817,8 @@ __device__ __forceinline__ void score_trip_half(const DenseP& dn, const double2*
     acc += (double)t[0];
 }
 // -> the item's cost in lane 31 (first item) and lane 63 (second item) only
-template <bool BYTE>
+// REDUCE false: every lane's own sum instead (pair_half_sum below makes the costs of it)
+template <bool BYTE, bool REDUCE = true>
 __device__ __forceinline__ double eval_pair_half(const DenseP& dn, const double2* __restrict__ pts, int n, const DenseItem& it) {
   double acc = 0.;
   const int n_pad = round_up(n, 32), chunks = n_pad >> 5;
@@ -791,6 +846,7 @@ __device__ __forceinline__ double eval_pair_half(const DenseP& dn, const double2
       base += u * 32;
     }
   }
+  if constexpr (!REDUCE) return acc;
   double v = acc;
   v += dpp_f64<0xB1>(v);
   v += dpp_f64<0x4E>(v);
@@ -799,11 +855,21 @@ __device__ __forceinline__ double eval_pair_half(const DenseP& dn, const double2
   v += dpp_bcast_f64<0x142, 0xa>(v);  // row_bcast:15: lane 31 = rows 0 + 1, lane 63 = rows 2 + 3
   return -v;
 }
+// (the reduction of eval_pair_half by itself, for the evaluations the quick decision leaves over: the same five steps)
+__device__ __forceinline__ double pair_half_sum(double v) {
+  v += dpp_f64<0xB1>(v);
+  v += dpp_f64<0x4E>(v);
+  v += dpp_f64<0x141>(v);
+  v += dpp_f64<0x140>(v);
+  v += dpp_bcast_f64<0x142, 0xa>(v);
+  return -v;
+}
 
 // the same with the folded constants already at hand (the PSO keeps them with each proposal)
 // NOCLIP: the kernel was chosen by the host for a grid whose cells do not overhang the frame (DenseP::clip == 0), and
 // carries none of the clipping variants of the trips.
-template <bool WIDE, bool BYTE, bool NOCLAMP = false, bool NOCLIP = false>
+// REDUCE false: the lane's own sum, not reduced and not negated -- the caller decides how (quick decision, eval_items)
+template <bool WIDE, bool BYTE, bool NOCLAMP = false, bool NOCLIP = false, bool REDUCE = true>
 __device__ __forceinline__ double eval_item_wave_dense(const GridP& g, const DenseP& dn, const unsigned char* lds0,
                                                        const double2* __restrict__ pts, int n, const DenseItem& it) {
   constexpr int U = NDTPSO_UNROLL;
@@ -815,7 +881,7 @@ __device__ __forceinline__ double eval_item_wave_dense(const GridP& g, const Den
     // (a grid whose last cells overhang the frame: the guard keeps scan B's disc below the frame's upper bounds as well --
     // k_align_pairs --, so no point of a pose under it can fail the clip test and the trips need not make it)
     noclamp_trips<false, BYTE>(g, dn, lds0, pts, n, n_pad, it, acc);
-    return -wave_sum(acc[0]);
+    return REDUCE ? -wave_sum(acc[0]) : acc[0];
   }
   // a 2048-beam list (BASELINE config 5; 32 chunks, entries in 16-byte units) in six-chunk trips, as the no-clamp loop
   // scores 17 chunks (noclamp_trips): 6 + 6 + 6 + 6 + 4 + 4, straight-line, folded in the four-chunk order
@@ -828,7 +894,7 @@ __device__ __forceinline__ double eval_item_wave_dense(const GridP& g, const Den
       score_trip_dense<6, false, false, BYTE, false, false, kFoldCarryGroup>(g, dn, lds0, pts, 18 * kWave, n, it, acc, nullptr, &carry);
       score_trip_dense<4, false, false, BYTE>(g, dn, lds0, pts, 24 * kWave, n, it, acc, nullptr);
       score_trip_dense<4, false, false, BYTE>(g, dn, lds0, pts, 28 * kWave, n, it, acc, nullptr);
-      return -wave_sum(acc[0]);
+      return REDUCE ? -wave_sum(acc[0]) : acc[0];
     }
   }
   // a remainder of exactly five chunks (1081 beams are 17) goes as one trip instead of a trip of four and a lonely one
@@ -857,7 +923,7 @@ __device__ __forceinline__ double eval_item_wave_dense(const GridP& g, const Den
       }
     for (; base < n_pad; base += kWave) score_trip_dense<1, false, false, BYTE>(g, dn, lds0, pts, base, n, it, acc, nullptr);
   }
-  return -wave_sum(acc[0]);
+  return REDUCE ? -wave_sum(acc[0]) : acc[0];
 }
 
 template <bool DUMP, bool WIDE = false, bool BYTE = false>
@@ -2167,6 +2233,27 @@ __device__ __forceinline__ void near_note(int* near_cnt, unsigned short* near_li
 }
 __device__ __forceinline__ bool near_tie(double a, double b, double tau) { return fabs(a - b) <= tau; }
 
+// The quick decision's test (wave_sum_f32).  c32 = -(the fp32 lane sum) lies within eps = quick_eps(n) of the
+// cost c the full reduce would give.  A CLEAR LOSER is worse than BOTH its pbest's cost and the gbest's by more than
+// tau + 2 eps (tau = 0 without arbitration): then c - pbc_j and c - gbc exceed tau + eps, so c is neither an improver nor
+// a near tie, and c32 -- which is what gets stored -- exceeds both by more than tau as well, so every later reader of the
+// stored cost in pso_run_wg answers as it would for c: the near-tie list read off the stored costs (|c32 - .| > tau),
+// the commit's `cost < pbc` (false), and the improver scans behind an arbitration -- those compare with the gbest's fp64
+// score, which lies within tau / 2 of the gbc the test saw (the margin's own premise), and with a pbc that only listed
+// items -- near ties, never a clear loser -- had replaced.  A phase that goes on behind an arbitration evaluates its items
+// again, against the new gbc and tau.  Without arbitration the underflow test is answered as well: c32 < -2 eps puts c
+// below -kTinyCost.  A NaN fails every comparison here and takes the full path, as does anything closer than the slack.
+template <bool ARB>
+__device__ __forceinline__ bool quick_loser(double c32, double pbc_j, double gbc, int n) {
+  const double slack = (ARB ? arb_margin(gbc, n) : 0.) + 2. * quick_eps(n);  // (uniform)
+  // min(c32 - pbc_j, c32 - gbc).  A NaN pbest -- it never takes a cost over -- leaves the gbest's side, as fmax would; the
+  // instruction is spelt out because fmax() came with a canonicalising v_max_f64 x, x in front of each operand
+  double worst;
+  asm("v_max_f64 %0, %1, %2" : "=v"(worst) : "v"(pbc_j), "v"(gbc));
+  const bool worse = c32 - worst > slack;
+  return ARB ? worse : (worse && c32 < -slack);
+}
+
 // The fp64 scores of an arbitration, one task per wave.  Deliberately NOT inlined and not a template: one copy in the
 // library, called from the cold blocks of the fp32-score kernels with its parameter block in LDS -- the fp64 score
 // loop inlined into them cost the hot loop its registers (private segment 0 -> 208 bytes, -17 % throughput).
@@ -2689,6 +2776,9 @@ __device__ inline void eval_items(const EvalCtx& E, const double2* pts, int n, c
                                   int last /*exclusive*/, double gbc, int* improver, int* tiny, int* near_cnt,
                                   unsigned short* near_list) {
   const int n_waves = blockDim.x >> 6;
+  // the quick decision (quick_loser): the dense forms hand back the lane's sum, and only what is no clear loser is reduced in fp64
+  constexpr bool kQ = kQuickDecide && MODE == kScoreF32 && path_is_dense(PATH);
+  if constexpr (kQ) settle_vmem();
   int j0, dj, jend;
   if constexpr (KGEN) {
     // E.light = k >= 2 items per other wave: a round of k (n - 1) + 1 items; wave w >= 1 takes items w - 1, w - 1 + (n - 1),
@@ -2723,12 +2813,12 @@ __device__ inline void eval_items(const EvalCtx& E, const double2* pts, int n, c
 #ifdef NDTPSO_COUNT_NOCLAMP  // diagnostic builds: evaluations through the no-clamp loop, reported as `gbest_updates`
           if (lane_id() == 0) atomicAdd(tiny + 2, 1);  // PsoShared::timed_out (unused by a single workgroup)
 #endif
-          cost = eval_item_wave_dense<false, PATH == 3, true, NOCLIP>(E.g, E.dn, E.lds0, pts, n, it);
+          cost = eval_item_wave_dense<false, PATH == 3, true, NOCLIP, !kQ>(E.g, E.dn, E.lds0, pts, n, it);
         }
         else
-          cost = eval_item_wave_dense<false, PATH == 3, false, NOCLIP>(E.g, E.dn, E.lds0, pts, n, it);
+          cost = eval_item_wave_dense<false, PATH == 3, false, NOCLIP, !kQ>(E.g, E.dn, E.lds0, pts, n, it);
       } else {
-        cost = eval_item_wave_dense<false, PATH == 3, false, NOCLIP>(E.g, E.dn, E.lds0, pts, n, it);
+        cost = eval_item_wave_dense<false, PATH == 3, false, NOCLIP, !kQ>(E.g, E.dn, E.lds0, pts, n, it);
       }
     } else {
       const double tx = sw.tpos[j], ty = sw.tpos[S + j];
@@ -2747,6 +2837,21 @@ __device__ inline void eval_items(const EvalCtx& E, const double2* pts, int n, c
       } else {
         cost = eval_pose_wave<MODE, (PATH & 3) == 1>(E.g, E.wn, E.T, pts, n, c, s, tx, ty);
       }
+    }
+    if constexpr (kQ) {  // (`cost` is the lane's sum so far)
+      if (improver) {    // (the swarm's initialisation keeps every cost: a pbest's)
+        const double c32 = -(double)wave_sum_f32((float)cost);
+        if (__builtin_amdgcn_ballot_w64(quick_loser<ARB>(c32, pbc_j, gbc, n)) != 0) {  // (the same answer in every lane)
+          if (lane_id() == 0) {
+            sw.tcost[j] = c32;
+#ifdef NDTPSO_COUNT_QUICK  // diagnostic builds: evaluations decided quickly, reported as `gbest_updates` (against `cost_evals`)
+            atomicAdd(tiny + 2, 1);  // PsoShared::timed_out (unused by a single workgroup)
+#endif
+          }
+          continue;
+        }
+      }
+      cost = -wave_sum(cost);
     }
 #ifdef NDTPSO_VERIFY_MARGIN
     if constexpr (ARB && (PATH == 2 || PATH == 3))
@@ -2826,6 +2931,8 @@ __device__ inline void eval_stream(const EvalCtx& E, const double2* pts, int n, 
                                    int* ticket, int* spare, int* improver, int* jmax, int* tiny, int* near_cnt,
                                    unsigned short* near_list) {
   typedef int __attribute__((address_space(3))) * lds_int_t;
+  constexpr bool kQ = kQuickDecide && MODE == kScoreF32 && path_is_dense(PATH);  // (the quick decision, as eval_items)
+  if constexpr (kQ) settle_vmem();
   int last_done = -1;
   if constexpr (PAIR) {
     // ---- two items per wave (eval_pair_half): tickets j and j + 1 at once ----
@@ -2886,7 +2993,26 @@ __device__ inline void eval_stream(const EvalCtx& E, const double2* pts, int n, 
         const int jl = (second && has_b) ? j + 1 : j;
         const DenseItem it{sw.it[4 * jl], sw.it[4 * jl + 1], sw.it[4 * jl + 2], sw.it[4 * jl + 3], E.dn.xmax, E.dn.ymax};
         const double pbc_l = sw.pbc[jl];
-        const double cost = eval_pair_half<PATH == 3>(E.dn, pts, n, it);
+        double cost;
+        if constexpr (kQ) {
+          // the two halves' fp32 sums in lanes 31 and 63 (five levels: quick_eps covers them); only when BOTH items are
+          // clear losers is the fp64 reduce left out -- it is one sequence for the two
+          const double lsum = eval_pair_half<PATH == 3, false>(E.dn, pts, n, it);
+          const double c32 = -(double)wave_sum_f32<5>((float)lsum);
+          const bool holder = (lane_id() & 31) == 31 && (!second || has_b);
+          if (__builtin_amdgcn_ballot_w64(holder && !quick_loser<ARB>(c32, pbc_l, gbc, n)) == 0) {
+            if (holder) {
+              sw.tcost[jl] = c32;
+#ifdef NDTPSO_COUNT_QUICK
+              atomicAdd(tiny + 1, 1);  // PsoShared::timed_out, as the one-item loop
+#endif
+            }
+            continue;
+          }
+          cost = pair_half_sum(lsum);
+        } else {
+          cost = eval_pair_half<PATH == 3>(E.dn, pts, n, it);
+        }
 #ifdef NDTPSO_VERIFY_MARGIN
         if constexpr (ARB) {
           if (E.xa) {  // (both items' fp32 scores against their fp64 scores and the bound, as the one-item loop does)
@@ -2904,9 +3030,22 @@ __device__ inline void eval_stream(const EvalCtx& E, const double2* pts, int n, 
           const double pbc_q = sw.pbc[jq];
           double cost;
           if (q == 0 ? g_a : g_b)
-            cost = eval_item_wave_dense<false, PATH == 3, true, NOCLIP>(E.g, E.dn, E.lds0, pts, n, it);
+            cost = eval_item_wave_dense<false, PATH == 3, true, NOCLIP, !kQ>(E.g, E.dn, E.lds0, pts, n, it);
           else
-            cost = eval_item_wave_dense<false, PATH == 3, false, NOCLIP>(E.g, E.dn, E.lds0, pts, n, it);
+            cost = eval_item_wave_dense<false, PATH == 3, false, NOCLIP, !kQ>(E.g, E.dn, E.lds0, pts, n, it);
+          if constexpr (kQ) {  // (`cost` is the lane's sum so far, as in the one-item loop)
+            const double c32 = -(double)wave_sum_f32((float)cost);
+            if (__builtin_amdgcn_ballot_w64(quick_loser<ARB>(c32, pbc_q, gbc, n)) != 0) {
+              if (lane_id() == 0) {
+                sw.tcost[jq] = c32;
+#ifdef NDTPSO_COUNT_QUICK
+                atomicAdd(tiny + 1, 1);
+#endif
+              }
+              continue;
+            }
+            cost = -wave_sum(cost);
+          }
           if (lane_id() == 0) decide(jq, cost, pbc_q);
         }
       }
@@ -2955,12 +3094,12 @@ __device__ inline void eval_stream(const EvalCtx& E, const double2* pts, int n, 
 #ifdef NDTPSO_COUNT_NOCLAMP
           if (lane_id() == 0) atomicAdd(tiny + 1, 1);  // (`tiny` is PsoShared::tiny_j here) PsoShared::timed_out, as eval_items
 #endif
-          cost = eval_item_wave_dense<false, PATH == 3, true, NOCLIP>(E.g, E.dn, E.lds0, pts, n, it);
+          cost = eval_item_wave_dense<false, PATH == 3, true, NOCLIP, !kQ>(E.g, E.dn, E.lds0, pts, n, it);
         }
         else
-          cost = eval_item_wave_dense<false, PATH == 3, false, NOCLIP>(E.g, E.dn, E.lds0, pts, n, it);
+          cost = eval_item_wave_dense<false, PATH == 3, false, NOCLIP, !kQ>(E.g, E.dn, E.lds0, pts, n, it);
       } else {
-        cost = eval_item_wave_dense<false, PATH == 3, false, NOCLIP>(E.g, E.dn, E.lds0, pts, n, it);
+        cost = eval_item_wave_dense<false, PATH == 3, false, NOCLIP, !kQ>(E.g, E.dn, E.lds0, pts, n, it);
       }
     } else {
       const double tx = sw.tpos[j], ty = sw.tpos[S + j];
@@ -2985,6 +3124,19 @@ __device__ inline void eval_stream(const EvalCtx& E, const double2* pts, int n, 
       if (E.xa) verify_item<PATH == 3>(E.xa, j, cost, gbc);
 #endif
     last_done = j;
+    if constexpr (kQ) {  // (`cost` is the lane's sum so far: a clear loser is done here, see eval_items)
+      const double c32 = -(double)wave_sum_f32((float)cost);
+      if (__builtin_amdgcn_ballot_w64(quick_loser<ARB>(c32, pbc_j, gbc, n)) != 0) {
+        if (lane_id() == 0) {
+          sw.tcost[j] = c32;
+#ifdef NDTPSO_COUNT_QUICK
+          atomicAdd(tiny + 1, 1);  // (`tiny` is PsoShared::tiny_j here) PsoShared::timed_out, as eval_items
+#endif
+        }
+        continue;
+      }
+      cost = -wave_sum(cost);
+    }
     if (lane_id() == 0) {  // (as eval_items, with an improver to look for)
       sw.tcost[j] = cost;
       bool ordinary = true;
@@ -4012,7 +4164,7 @@ __device__ inline bool pso_run_wg(const EvalCtx& E,
       stats->rounds = arb_ticks;
 #endif
       stats->gbest_updates = n_gb;
-#if defined(NDTPSO_COUNT_AMBIG) || defined(NDTPSO_COUNT_NOCLAMP)
+#if defined(NDTPSO_COUNT_AMBIG) || defined(NDTPSO_COUNT_NOCLAMP) || defined(NDTPSO_COUNT_QUICK)
       if (!CLUSTER) stats->gbest_updates = (uint32_t)sh->timed_out;
 #endif
     }
