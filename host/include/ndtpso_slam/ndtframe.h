@@ -41,6 +41,15 @@ struct NDTAlignRequest {
   bool ok;        // out
 };
 
+// What NDTFrame::relocalize returns (not in the reference): the refined pose of lowest cost and that cost, the lattice hits that
+// were refined, and whether the device did it (false: `pose` is the lattice's origin, the error is recorded, status.h).
+struct NDTRelocalizeResult {
+  Vector3d pose;
+  double cost;
+  unsigned hits;
+  bool ok;
+};
+
 // One request of NDTFrame::loadLaserBatch (not in the reference): frame->loadLaser(*laser_data, min_angle, angle_increment, max_range).
 struct NDTLoadRequest {
   NDTFrame* frame;
@@ -110,6 +119,19 @@ class NDTFrame {
   // result), and so does a frame that one request aligns against and another aligns as scan; any other request takes align() itself, in its place.  The reference aligns one scan at a time
   // (ndtpso_slam_node.cpp:182-194).
   static void alignBatch(NDTAlignRequest* reqs, size_t n);
+  // Where in this frame was `new_frame` taken, when no guess within align()'s +-0.1 m / +-3 mrad (ndtframe.cpp:253) is known: a
+  // robot switched on inside a known map, a lost track, a loop closure.  The scan is scored at every node of the pose lattice
+  // origin + (i, j, k) * step, i < count[0], j < count[1], k < count[2] (ndtpso_map_search, include/ndtpso_hip.h, in the
+  // library's score mode); each of the best top_k nodes (1 .. 64), in hit order, is then refined by pso_optimization from the node
+  // with a deviation of step / 2 per axis (on an axis of one node: align()'s first-call deviation on that axis), the configuration
+  // align() would use and one table of the thread's rand() stream each, all in ONE launch (ndtpso_map_align_batch); the refined
+  // pose of lowest cost is returned, ties to the earlier hit.  The frame then tracks from there as a fresh one would: the next
+  // two align() calls use the first-call deviation.  On failure -- a frame that is not resident, a scan of another thread's
+  // context, a device call that fails -- the result is {origin, 0, 0, false}, the error is recorded (ndtpso_slam/status.h), a
+  // following update() is refused as after a failed align(), and the tracking state is untouched.  The rand() tables are drawn
+  // once the hits are known, even if the refinement then fails (as optimize() draws).
+  NDTRelocalizeResult relocalize(const NDTFrame* new_frame, const Vector3d& origin, const Vector3d& step, const unsigned count[3],
+                                 unsigned top_k);
   // Several loadLaser() / update() calls at once: observably identical to the member calls in request order -- `built`, the
   // refusal of an update() after a failed align() with its count (updatesRefused()) and recorded error, the rule for the
   // speculative build, every error recorded as the member call records it -- but consecutive requests that qualify share their

@@ -693,6 +693,75 @@ void NDTFrame::alignBatch(NDTAlignRequest* reqs, size_t n) {
   }
 }
 
+// A pose lattice searched on the device, its best nodes refined in one launch (see ndtframe.h).
+NDTRelocalizeResult NDTFrame::relocalize(const NDTFrame* new_frame, const Vector3d& origin, const Vector3d& step,
+                                         const unsigned count[3], unsigned top_k) {
+  const NDTRelocalizeResult failed{origin, 0., 0u, false};
+  auto refuse = [&](int rc, const char* what) {
+    ndtpso_host::check(rc, what);
+    recordAlignOutcome(false);
+    return failed;
+  };
+  if (!new_frame || !count) return refuse(NDTPSO_E_ARG, "relocalize: null argument");
+  if (!s_resident) return refuse(NDTPSO_E_STATE, "relocalize: the frame is not resident");
+  if (new_frame->dev() != dev()) return refuse(NDTPSO_E_ARG, "relocalize: a scan of another thread's context");
+  ndtpso_host::Use use(dev());
+  ndtpso_map* m = ensureMap();
+  if (!m) return refuse(NDTPSO_E_STATE, "relocalize: no device map");
+  std::vector<double> unused;
+  const DeviceScan scan(new_frame, false, unused, "relocalize");
+  ndtpso_lattice lat;
+  std::memset(&lat, 0, sizeof(lat));
+  for (int a = 0; a < 3; ++a) {
+    lat.origin[a] = origin[a];
+    lat.step[a] = step[a];
+    lat.count[a] = count[a];
+  }
+  lat.top_k = top_k;
+  ndtpso_lattice_hit hits[NDTPSO_SEARCH_MAX_TOP_K];
+  uint32_t n_hits = 0;
+  if (!ndtpso_host::check(ndtpso_map_search(m, scan.pts, &lat, ndtpso_host::score_mode(), hits, &n_hits, nullptr), "relocalize")) {
+    recordAlignOutcome(false);
+    return failed;
+  }
+  const ndtpso_pso_config abi = to_abi(align_uses_frame_config() ? s_config.psoConfig : PSOConfig());
+  const size_t n_draw = ndtpso_rand_draws(&abi);
+  std::vector<ndtpso_map_align_job> jobs(n_hits);
+  std::vector<int32_t> draws(n_hits * n_draw);
+  std::memset(jobs.data(), 0, jobs.size() * sizeof(ndtpso_map_align_job));
+  const double first_call[3] = {.1, .1, 3.1415E-3};  // (nextDeviation's)
+  for (uint32_t k = 0; k < n_hits; ++k) {
+    ndtpso_map_align_job& job = jobs[k];
+    job.map = m;
+    job.new_points = scan.pts;
+    ndtpso_host::draw_rand(&draws[k * n_draw], n_draw);  // drawn even if the device call fails (optimize)
+    job.rand_table = &draws[k * n_draw];
+    job.flags = 1u;  // cost wanted
+    for (int a = 0; a < 3; ++a) {
+      job.guess[a] = job.pose[a] = hits[k].pose[a];
+      job.deviation[a] = count[a] > 1 ? step[a] / 2. : first_call[a];
+    }
+  }
+  const int rc_call = ndtpso_map_align_batch(ndtpso_host::device(), jobs.data(), n_hits, &abi, ndtpso_host::score_mode());
+  bool some_job_failed = false;
+  for (uint32_t k = 0; k < n_hits; ++k) some_job_failed = some_job_failed || jobs[k].rc != NDTPSO_OK;
+  // (a call refused as a whole failed every job, as in alignBatch)
+  if (rc_call != NDTPSO_OK && !some_job_failed) return refuse(rc_call, "relocalize");
+  int best = -1;
+  for (uint32_t k = 0; k < n_hits; ++k)
+    if (jobs[k].rc == NDTPSO_OK && (best < 0 || jobs[k].cost < jobs[(size_t)best].cost)) best = (int)k;
+  if (best < 0) return refuse(rc_call != NDTPSO_OK ? rc_call : NDTPSO_E_HIP, "relocalize");
+  Vector3d pose(jobs[(size_t)best].pose[0], jobs[(size_t)best].pose[1], jobs[(size_t)best].pose[2]);
+#if TRANSFORM_POSE_AFTER_ALIGN
+  pose -= s_trans;
+#endif
+  s_prev_pose = pose;
+  s_pose_diff = Vector3d::Zero();
+  s_iter = 0;
+  recordAlignOutcome(true);
+  return NDTRelocalizeResult{pose, jobs[(size_t)best].cost, n_hits, true};
+}
+
 // Several loadLaser() calls (see ndtframe.h): the member's own steps per request, with ONE ndtpso_points_load_scans for a run of
 // requests on per-scan frames.
 void NDTFrame::loadLaserBatch(NDTLoadRequest* reqs, size_t n) {

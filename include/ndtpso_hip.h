@@ -382,6 +382,74 @@ int ndtpso_map_update_batch(ndtpso_ctx *ctx, ndtpso_map_update_job *jobs, uint32
 /* cost_function (core.cpp:26-48) of a loaded scan against the map at n_poses candidate poses (3 doubles each) */
 int ndtpso_map_cost(ndtpso_map *map, ndtpso_points *new_points, const double *poses, uint32_t n_poses, int score_mode,
                     double *costs);
+/* cost_function (core.cpp:26-48) at every node of a pose lattice, and the best top_k nodes: the start poses of a
+ * relocalization, where a guess is a metre or a radian off and ndtpso_map_align's +-0.1 m / +-3 mrad search (ndtframe.cpp:253)
+ * would settle in the wrong basin.  The reference has no counterpart; a call stands for nx * ny * nth cost_function calls.
+ *   - Node numbering: node (i, j, k) has index (k * ny + j) * nx + i.
+ *   - Node pose: each component is origin + (double)i * step -- one multiplication, one addition, no FMA -- so a caller
+ *     regenerates any node's pose bit for bit.  On an axis of one node the step is not read (the pose is origin + 0.).
+ *   - Returned: *n_hits = min(top_k, n_nodes) hits in ascending cost, ties broken by ascending index.  A NaN cost ranks behind
+ *     every number, NaNs among themselves by index.  Comparison is by value: -0. and +0. tie.  `hits` has room for top_k.
+ *   - The map: built first if points were inserted since the last build, a pending speculation committed, exactly as
+ *     ndtpso_map_cost does; synchronous; the map is left in the state ndtpso_map_cost would leave it in.
+ *   - NDTPSO_SCORE_F64: every hit's cost is bit for bit what ndtpso_map_cost(map, new_points, hit.pose, 1, F64, ...) returns,
+ *     and the hits are exactly the best n_hits of that function over all nodes (one wave per node, the four lane accumulators
+ *     and the wave sum of the cost kernel: the summation order is the same).
+ *   - NDTPSO_SCORE_F32: the fp32 sweep's own best nodes with their fp32 costs -- a tolerance mode, as everywhere.
+ *   - NDTPSO_SCORE_EXACT: the F64 result bit for bit, from the fp32 sweep wherever its margin is proven: sweep in fp32, take the
+ *     K-th smallest fp32 cost c32_K (K = n_hits), collect every node with c32 <= c32_K + 7e-7 * n_points, score those in fp64
+ *     through ndtpso_map_cost's path, rank.  (The fp32 sum is within 2.95e-7 * n_points of the fp64 one, so the true K-th cost
+ *     is <= c32_K + B and every true member has c32 <= c32_K + 2 B < c32_K + tau: DESIGN 3.5.)  The whole lattice runs in fp64
+ *     instead -- stats->fell_back says why -- when the plan is not the dense table, when an fp32 cost is NaN, when c32_K lies in
+ *     the fp32 underflow regime (> -1e-28), when more than NDTPSO_SEARCH_MAX_CANDIDATES nodes qualify, or when the process was
+ *     refused the exact mode by the start-up check.
+ * Nothing proportional to the node count crosses the host link: the node poses come from the descriptor, the selection runs on
+ * the device (a cost per node stays in device memory: 8 bytes x nodes).
+ * Errors, before anything is enqueued: NDTPSO_E_ARG for a null pointer, a count of 0, more than 2^24 nodes, top_k outside
+ * 1 .. 64, a step that is not positive and finite on an axis of more than one node, a non-finite origin, a scan of another
+ * context or a bad score mode; NDTPSO_E_CAPACITY when the plan does not fit, as ndtpso_map_cost says it. */
+typedef struct {
+  double origin[3];  /* pose of node (0,0,0): x, y, theta */
+  double step[3];    /* > 0 and finite on every axis whose count > 1 */
+  uint32_t count[3]; /* nx, ny, nth, each >= 1; nx*ny*nth <= 2^24 */
+  uint32_t top_k;    /* 1 .. 64 */
+} ndtpso_lattice;
+typedef struct {
+  double pose[3];
+  double cost;
+  uint32_t index, reserved;
+} ndtpso_lattice_hit;
+typedef struct {
+  uint32_t n_nodes, n_points;
+  uint32_t mode_run;     /* the score the sweep ran with: NDTPSO_SCORE_F32 or NDTPSO_SCORE_F64 */
+  uint32_t path;         /* table plan: 0 / 1 bitmap (division / power-of-two cells), 2 dense, 4 / 5 as 0 / 1 from the HBM image */
+  uint32_t n_candidates; /* EXACT: nodes rescored in fp64 */
+  uint32_t fell_back;    /* EXACT: why the fp64 sweep ran instead (NDTPSO_SEARCH_FELL_*), 0 = it did not */
+  uint32_t reserved[2];
+} ndtpso_search_stats;
+#define NDTPSO_LATTICE_BYTES 64
+#define NDTPSO_LATTICE_HIT_BYTES 40
+#define NDTPSO_SEARCH_STATS_BYTES 32
+#define NDTPSO_SEARCH_MAX_NODES (1u << 24)
+#define NDTPSO_SEARCH_MAX_TOP_K 64
+#define NDTPSO_SEARCH_MAX_CANDIDATES 4096
+#define NDTPSO_SEARCH_FELL_PLAN 1      /* the plan is not the dense table */
+#define NDTPSO_SEARCH_FELL_NAN 2       /* an fp32 cost is NaN */
+#define NDTPSO_SEARCH_FELL_UNDERFLOW 3 /* c32_K lies in the fp32 underflow regime */
+#define NDTPSO_SEARCH_FELL_MANY 4      /* more than NDTPSO_SEARCH_MAX_CANDIDATES candidates */
+#define NDTPSO_SEARCH_FELL_REFUSED 5   /* the start-up check refused the exact mode */
+#if defined(__cplusplus)
+static_assert(sizeof(ndtpso_lattice) == NDTPSO_LATTICE_BYTES, "ndtpso_lattice layout");
+static_assert(sizeof(ndtpso_lattice_hit) == NDTPSO_LATTICE_HIT_BYTES, "ndtpso_lattice_hit layout");
+static_assert(sizeof(ndtpso_search_stats) == NDTPSO_SEARCH_STATS_BYTES, "ndtpso_search_stats layout");
+#elif defined(__STDC_VERSION__) && __STDC_VERSION__ >= 201112L
+_Static_assert(sizeof(ndtpso_lattice) == NDTPSO_LATTICE_BYTES, "ndtpso_lattice layout");
+_Static_assert(sizeof(ndtpso_lattice_hit) == NDTPSO_LATTICE_HIT_BYTES, "ndtpso_lattice_hit layout");
+_Static_assert(sizeof(ndtpso_search_stats) == NDTPSO_SEARCH_STATS_BYTES, "ndtpso_search_stats layout");
+#endif
+/* (stands for nx * ny * nth calls of cost_function, core.cpp:26-48) */
+int ndtpso_map_search(ndtpso_map *map, ndtpso_points *new_points, const ndtpso_lattice *lattice, int score_mode,
+                      ndtpso_lattice_hit *hits, uint32_t *n_hits, ndtpso_search_stats *stats /* may be NULL */);
 int ndtpso_map_get_info(ndtpso_map *map, ndtpso_map_info *info);
 /* created cells in ascending index order (row.reserved = the cell's current window slot) */
 int ndtpso_map_get_cells(ndtpso_map *map, ndtpso_cell_row *rows, uint32_t max_rows, uint32_t *n_rows);

@@ -115,6 +115,40 @@ class MapUpdateJob(C.Structure):
                 ("rc", C.c_int32), ("route", C.c_int32), ("reserved", C.c_int32)]
 
 
+class Lattice(C.Structure):
+    """ndtpso_lattice (include/ndtpso_hip.h): the pose lattice of ndtpso_map_search"""
+    _fields_ = [("origin", C.c_double * 3), ("step", C.c_double * 3), ("count", C.c_uint32 * 3), ("top_k", C.c_uint32)]
+
+
+class LatticeHit(C.Structure):
+    """ndtpso_lattice_hit"""
+    _fields_ = [("pose", C.c_double * 3), ("cost", C.c_double), ("index", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+class SearchStats(C.Structure):
+    """ndtpso_search_stats"""
+    _fields_ = [("n_nodes", C.c_uint32), ("n_points", C.c_uint32), ("mode_run", C.c_uint32), ("path", C.c_uint32),
+                ("n_candidates", C.c_uint32), ("fell_back", C.c_uint32), ("reserved", C.c_uint32 * 2)]
+
+
+SEARCH_MAX_TOP_K = 64
+SEARCH_MAX_CANDIDATES = 4096
+# SearchStats.fell_back (NDTPSO_SEARCH_FELL_*): why SCORE_EXACT swept the lattice in fp64
+SEARCH_FELL_PLAN, SEARCH_FELL_NAN, SEARCH_FELL_UNDERFLOW, SEARCH_FELL_MANY, SEARCH_FELL_REFUSED = 1, 2, 3, 4, 5
+
+
+def lattice_poses(origin, step, count) -> np.ndarray:
+    """Every node's pose, [nx * ny * nth, 3], by ndtpso_map_search's contract: node (i, j, k) has index (k * ny + j) * nx + i and
+    each component is origin + float(i) * step -- one multiplication, one addition, the device's bits.  On an axis of one node
+    the step is not read."""
+    origin = np.asarray(origin, dtype=np.float64).reshape(3)
+    count = [int(c) for c in count]
+    step = [float(s) if c > 1 else 0.0 for s, c in zip(step, count)]
+    axes = [origin[a] + np.arange(count[a], dtype=np.float64) * step[a] for a in range(3)]
+    th, y, x = np.meshgrid(axes[2], axes[1], axes[0], indexing="ij")
+    return np.stack([x.ravel(), y.ravel(), th.ravel()], axis=1)
+
+
 STATS_DTYPE = np.dtype([("n_points", "<u4"), ("n_built", "<u4"), ("cost_evals", "<u4"), ("rounds", "<u4"),
                         ("gbest_updates", "<u4"), ("status", "<u2"), ("arbitrated", "<u2"), ("t_start", "<u4"),
                         ("t_end", "<u4")])   # the C struct's `status` word: flags in its low half, SCORE_EXACT's count above
@@ -129,7 +163,7 @@ EXPORTS = [
     "ndtpso_align_pairs_dev", "ndtpso_align_pairs_footprint", "ndtpso_align_pairs_describe",
     "ndtpso_points_create", "ndtpso_points_destroy", "ndtpso_points_load_scan", "ndtpso_points_set", "ndtpso_points_get",
     "ndtpso_map_create", "ndtpso_map_destroy", "ndtpso_map_reset", "ndtpso_map_clear", "ndtpso_map_mark_unbuilt", "ndtpso_map_insert", "ndtpso_map_insert_host",
-    "ndtpso_map_build", "ndtpso_map_speculate_build", "ndtpso_map_align", "ndtpso_map_cost", "ndtpso_map_get_info", "ndtpso_map_get_cells", "ndtpso_map_get_points",
+    "ndtpso_map_build", "ndtpso_map_speculate_build", "ndtpso_map_align", "ndtpso_map_cost", "ndtpso_map_search", "ndtpso_map_get_info", "ndtpso_map_get_cells", "ndtpso_map_get_points",
     "ndtpso_map_get_occupancy", "ndtpso_map_align_batch", "ndtpso_points_load_scans", "ndtpso_map_update_batch",
     "ndtpso_shard_group_create", "ndtpso_shard_group_destroy", "ndtpso_shard_group_size", "ndtpso_shard_last_error",
     "ndtpso_shard_range", "ndtpso_align_pairs_sharded", "ndtpso_align_pairs_sharded_dev", "ndtpso_shard_last_timing",
@@ -240,6 +274,8 @@ def load(build_if_missing: bool = True):
     L.ndtpso_map_update_batch.argtypes = [vp, C.POINTER(MapUpdateJob), C.c_uint32]
     L.ndtpso_exact_check_jobs.argtypes = [vp, C.POINTER(C.c_int)]
     L.ndtpso_map_cost.argtypes = [vp, vp, dp, C.c_uint32, C.c_int, dp]
+    L.ndtpso_map_search.argtypes = [vp, vp, C.POINTER(Lattice), C.c_int, C.POINTER(LatticeHit), C.POINTER(C.c_uint32),
+                                    C.POINTER(SearchStats)]
     L.ndtpso_map_get_info.argtypes = [vp, C.POINTER(MapInfo)]
     L.ndtpso_map_get_cells.argtypes = [vp, C.POINTER(CellRow), C.c_uint32, up]
     L.ndtpso_map_get_points.argtypes = [vp, C.c_int, dp, C.c_uint64, C.POINTER(C.c_uint64)]
@@ -828,6 +864,21 @@ class ResidentMap:
         self._ctx._chk(self._lib.ndtpso_map_cost(self._h, scan._h, _p(poses, C.c_double), poses.shape[0], mode,
                                                  _p(costs, C.c_double)))
         return costs
+
+    def search(self, scan: ResidentScan, origin, step, count, top_k, mode=SCORE_EXACT):
+        """ndtpso_map_search: the best top_k nodes of the pose lattice (lattice_poses(origin, step, count)) ->
+        (poses [K, 3], costs [K], index [K], stats dict), K = min(top_k, nodes), ascending cost then index."""
+        lat = Lattice((C.c_double * 3)(*[float(v) for v in origin]), (C.c_double * 3)(*[float(v) for v in step]),
+                      (C.c_uint32 * 3)(*[int(v) for v in count]), int(top_k))
+        hits = (LatticeHit * max(int(top_k), 1))()
+        n = C.c_uint32()
+        st = SearchStats()
+        self._ctx._chk(self._lib.ndtpso_map_search(self._h, scan._h, C.byref(lat), mode, hits, C.byref(n), C.byref(st)))
+        k = n.value
+        poses = np.array([h.pose[:] for h in hits[:k]], dtype=np.float64).reshape(k, 3)
+        costs = np.array([h.cost for h in hits[:k]], dtype=np.float64)
+        index = np.array([h.index for h in hits[:k]], dtype=np.uint32)
+        return poses, costs, index, {f: getattr(st, f) for f, _ in SearchStats._fields_ if f != "reserved"}
 
     def info(self) -> dict:
         i = MapInfo()

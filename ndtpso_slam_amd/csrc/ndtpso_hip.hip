@@ -617,6 +617,7 @@ struct ndtpso_ctx {
   void* jobs_pinned = nullptr;
   size_t jobs_pinned_cap = 0;
   DevBuf jobs_out, jobs_table;
+  DevBuf search_costs, search_keys, search_cand;  // ndtpso_map_search: a cost per node, the best-K lists, the exact mode's candidates
   uint32_t jobs_issued = 0;
   bool map_jobs_big_lds = false;      // ndtpso_map_update_batch: k_map_pack_jobs may take the whole LDS (set once per context)
 };
@@ -1092,7 +1093,8 @@ void ndtpso_ctx_destroy(ndtpso_ctx* c) {
   (void)hipSetDevice(c->device);
   (void)hipStreamSynchronize(c->stream);
   for (DevBuf* b : {&c->image, &c->rows, &c->xy, &c->xy2, &c->ranges, &c->ranges2, &c->poses, &c->costs, &c->dump,
-                    &c->small, &c->table, &c->out, &c->seeds, &c->ws, &c->gate, &c->cluster_xc, &c->ximg, &c->jobs_out, &c->jobs_table})
+                    &c->small, &c->table, &c->out, &c->seeds, &c->ws, &c->gate, &c->cluster_xc, &c->ximg, &c->jobs_out, &c->jobs_table,
+                    &c->search_costs, &c->search_keys, &c->search_cand})
     b->release();
   for (BeamDirs& b : c->beam_dirs) b.buf.release();
   c->pinned.release();

@@ -431,7 +431,10 @@ __device__ __forceinline__ void cell_coords_rt(const GridP& g, double qx, double
 // The body is branch-free (misses read slot 0 and are masked) and written phase by phase over U
 // points per lane, so the three dependent LDS round trips of U independent points overlap.
 // Returns the cost (-sum) on every lane.
-template <int MODE, bool POW2, int U, bool DUMP>
+// PREROT (the lattice sweep, ndtpso_map_search.hip): `pts` holds the scan already turned by the pose's heading -- fl(fl(x c) -
+// fl(y s)), fl(fl(x s) + fl(y c)), the reference's own intermediate values -- so the transform is the translation alone; c and
+// s are not read.  The fp64 score's terms are the unrotated form's bit for bit.
+template <int MODE, bool POW2, int U, bool DUMP, bool PREROT = false>
 __device__ __forceinline__ void score_trip(const GridP& g, const WinP& wn, const TableView& T,
                                            const double2* __restrict__ pts, int base, int n, double c, double s,
                                            double tx, double ty, double (&acc)[4], int32_t* __restrict__ dump) {
@@ -446,7 +449,10 @@ __device__ __forceinline__ void score_trip(const GridP& g, const WinP& wn, const
   int tagv[U];
 #pragma unroll
   for (int u = 0; u < U; ++u) {
-    if constexpr (MODE == kScoreF64) {
+    if constexpr (PREROT) {
+      qx[u] = p[u].x + tx;
+      qy[u] = p[u].y + ty;
+    } else if constexpr (MODE == kScoreF64) {
       qx[u] = (p[u].x * c - p[u].y * s) + tx;  // reference rounding, no fma
       qy[u] = (p[u].x * s + p[u].y * c) + ty;
     } else {
@@ -567,7 +573,9 @@ __device__ __forceinline__ DenseItem dense_item(const GridP& g, const DenseP& dn
 // complete that group, a whole group follows.  (Six-chunk trips: three dependent LDS round trips per trip is what a
 // wave waits for, so 17 chunks go as 6 + 6 + 5 instead of 4 + 4 + 4 + 5: + 4.8 % on the batch.)
 enum { kFoldByU = 0, kFoldSingles, kFoldGroupSingles, kFoldGroupCarry, kFoldCarryGroup };
-template <int U, bool DUMP, bool CLIP, bool BYTE = false, bool NOCLAMP = false, bool MASKLAST = false, int FOLD = kFoldByU>
+// PREROT: `pts` holds the scan already turned by the pose's heading (score_trip); it.C is 1 / cell_side and it.S is not read.
+template <int U, bool DUMP, bool CLIP, bool BYTE = false, bool NOCLAMP = false, bool MASKLAST = false, int FOLD = kFoldByU,
+          bool PREROT = false>
 __device__ __forceinline__ void score_trip_dense(const GridP& g, const DenseP& dn, const unsigned char* lds0,
                                                  const double2* __restrict__ pts, int base, int n,
                                                  const DenseItem& it, double (&acc)[4], int32_t* __restrict__ dump,
@@ -580,8 +588,13 @@ __device__ __forceinline__ void score_trip_dense(const GridP& g, const DenseP& d
   unsigned lin[U];
 #pragma unroll
   for (int u = 0; u < U; ++u) {
-    gx[u] = fma(p[u].x, it.C, fma(-p[u].y, it.S, it.TX));
-    gy[u] = fma(p[u].x, it.S, fma(p[u].y, it.C, it.TY));
+    if constexpr (PREROT) {
+      gx[u] = fma(p[u].x, it.C, it.TX);
+      gy[u] = fma(p[u].y, it.C, it.TY);
+    } else {
+      gx[u] = fma(p[u].x, it.C, fma(-p[u].y, it.S, it.TX));
+      gy[u] = fma(p[u].x, it.S, fma(p[u].y, it.C, it.TY));
+    }
     // Out-of-window coordinates clamp into the always-null high column / row (negative ones convert to huge
     // unsigned values first; column / row 0 is the empty low border): no range test, no select.
     const unsigned rx = NOCLAMP ? (unsigned)(int)gx[u] : min((unsigned)(int)gx[u], (unsigned)dn.dw),
@@ -684,7 +697,7 @@ __device__ __forceinline__ void score_trip_dense(const GridP& g, const DenseP& d
 
 // WIDE: a wave that has its SIMD to itself (cluster mode) keeps eight chunks in flight instead of four to cover the
 // LDS latency; the terms are folded in exactly the order of the U = 4 loop, so the sum is the same bit for bit.
-template <bool DUMP, bool CLIP, bool WIDE = false, bool BYTE = false>
+template <bool DUMP, bool CLIP, bool WIDE = false, bool BYTE = false, bool PREROT = false>
 __device__ __forceinline__ double eval_pose_wave_dense_c(const GridP& g, const DenseP& dn, const unsigned char* lds0,
                                                          const double2* __restrict__ pts, int n, double c, double s,
                                                          double tx, double ty, int32_t* __restrict__ dump) {
@@ -695,10 +708,11 @@ __device__ __forceinline__ double eval_pose_wave_dense_c(const GridP& g, const D
   int base = 0;
   if constexpr (WIDE && U == 4 && !DUMP)
     for (; base + 8 * kWave <= n_pad; base += 8 * kWave)
-      score_trip_dense<8, DUMP, CLIP, BYTE>(g, dn, lds0, pts, base, n, it, acc, dump);
+      score_trip_dense<8, DUMP, CLIP, BYTE, false, false, kFoldByU, PREROT>(g, dn, lds0, pts, base, n, it, acc, dump);
   for (; base + U * kWave <= n_pad; base += U * kWave)
-    score_trip_dense<U, DUMP, CLIP, BYTE>(g, dn, lds0, pts, base, n, it, acc, dump);
-  for (; base < n_pad; base += kWave) score_trip_dense<1, DUMP, CLIP, BYTE>(g, dn, lds0, pts, base, n, it, acc, dump);
+    score_trip_dense<U, DUMP, CLIP, BYTE, false, false, kFoldByU, PREROT>(g, dn, lds0, pts, base, n, it, acc, dump);
+  for (; base < n_pad; base += kWave)
+    score_trip_dense<1, DUMP, CLIP, BYTE, false, false, kFoldByU, PREROT>(g, dn, lds0, pts, base, n, it, acc, dump);
   return -wave_sum(acc[0]);
 }
 // The no-clamp loop's trips (DenseGuard).  The sum is the clamped sequence's bit for bit (score_trip_dense's FOLD);
@@ -926,12 +940,12 @@ __device__ __forceinline__ double eval_item_wave_dense(const GridP& g, const Den
   return REDUCE ? -wave_sum(acc[0]) : acc[0];
 }
 
-template <bool DUMP, bool WIDE = false, bool BYTE = false>
+template <bool DUMP, bool WIDE = false, bool BYTE = false, bool PREROT = false>
 __device__ __forceinline__ double eval_pose_wave_dense(const GridP& g, const DenseP& dn, const unsigned char* lds0,
                                                        const double2* __restrict__ pts, int n, double c, double s,
                                                        double tx, double ty, int32_t* __restrict__ dump) {
-  if (dn.clip) return eval_pose_wave_dense_c<DUMP, true, WIDE, BYTE>(g, dn, lds0, pts, n, c, s, tx, ty, dump);
-  return eval_pose_wave_dense_c<DUMP, false, WIDE, BYTE>(g, dn, lds0, pts, n, c, s, tx, ty, dump);
+  if (dn.clip) return eval_pose_wave_dense_c<DUMP, true, WIDE, BYTE, PREROT>(g, dn, lds0, pts, n, c, s, tx, ty, dump);
+  return eval_pose_wave_dense_c<DUMP, false, WIDE, BYTE, PREROT>(g, dn, lds0, pts, n, c, s, tx, ty, dump);
 }
 
 __device__ __forceinline__ double uniform_f64(double v) {  // a value every lane holds, moved to scalar registers
@@ -1247,7 +1261,7 @@ __device__ __forceinline__ double eval_pose_wave_d64(const GridP& g, const Dense
 }
 
 // pts must be padded to a multiple of kPointPad with out-of-frame sentinels (pad_points_wg)
-template <int MODE, bool POW2, bool DUMP, bool GUARD = false>
+template <int MODE, bool POW2, bool DUMP, bool GUARD = false, bool PREROT = false>
 __device__ __forceinline__ double eval_pose_wave_t(const GridP& g, const WinP& wn, const TableView& T,
                                                    const double2* __restrict__ pts, int n, double c, double s,
                                                    double tx, double ty, int32_t* __restrict__ dump) {
@@ -1256,15 +1270,16 @@ __device__ __forceinline__ double eval_pose_wave_t(const GridP& g, const WinP& w
   const int n_pad = round_up(n, kWave);
   int base = 0;
   static_assert(!GUARD || (MODE == kScoreF64 && !DUMP), "the guarded form is the fp64 score's, without cell dump");
+  static_assert(!GUARD || !PREROT, "the guarded trips turn the points themselves");
   if constexpr (GUARD) {  // (the same trips in the same order: the guarded form wherever a trip holds no padding)
     const double hwi = uniform_f64(g.hw * g.inv_cs), hhi = uniform_f64(g.hh * g.inv_cs);  // wave-uniform: scalar registers
     for (; base + U * kWave <= n; base += U * kWave)
       score_trip_guarded<POW2, U>(g, wn, T, pts, base, c, s, tx, ty, hwi, hhi, acc);
   }
   for (; base + U * kWave <= n_pad; base += U * kWave)
-    score_trip<MODE, POW2, U, DUMP>(g, wn, T, pts, base, n, c, s, tx, ty, acc, dump);
+    score_trip<MODE, POW2, U, DUMP, PREROT>(g, wn, T, pts, base, n, c, s, tx, ty, acc, dump);
   for (; base < n_pad; base += kWave)
-    score_trip<MODE, POW2, 1, DUMP>(g, wn, T, pts, base, n, c, s, tx, ty, acc, dump);
+    score_trip<MODE, POW2, 1, DUMP, PREROT>(g, wn, T, pts, base, n, c, s, tx, ty, acc, dump);
   return -wave_sum((acc[0] + acc[1]) + (acc[2] + acc[3]));
 }
 template <int MODE, bool POW2>

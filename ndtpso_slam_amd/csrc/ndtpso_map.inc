@@ -21,6 +21,7 @@
 #include "ndtpso_map_device.inc"
 
 #include "ndtpso_map_jobs.h"
+#include "ndtpso_map_search.h"
 
 // ---- the kernels of the single calls: one map (or one scan) each, the bodies in ndtpso_map_device.inc ---------------------
 __global__ void __launch_bounds__(kInsertThreads)
@@ -909,6 +910,12 @@ int ndtpso_map_cost(ndtpso_map* m, ndtpso_points* pts, const double* poses, uint
   return cost_launch(c, (const unsigned char*)m->image.p, m->p.g, window_of(m->host_hdr), (const double2*)pts->xy.p, n, poses, n_poses,
                      mode, costs, nullptr);
 }
+
+}  // extern "C"
+
+#include "ndtpso_map_search.inc"
+
+extern "C" {
 
 // ---- exports (shutdown / inspection; synchronous, the host walks the downloaded structures) -----------------------
 
