@@ -50,6 +50,16 @@ struct NDTRelocalizeResult {
   bool ok;
 };
 
+// One request of NDTFrame::relocalizeBatch (not in the reference): result = ref->relocalize(cur, origin, step, count, top_k).
+struct NDTRelocalizeRequest {
+  NDTFrame* ref;
+  const NDTFrame* cur;
+  Vector3d origin, step;
+  unsigned count[3];
+  unsigned top_k;
+  NDTRelocalizeResult result;  // out
+};
+
 // One request of NDTFrame::loadLaserBatch (not in the reference): frame->loadLaser(*laser_data, min_angle, angle_increment, max_range).
 struct NDTLoadRequest {
   NDTFrame* frame;
@@ -132,6 +142,18 @@ class NDTFrame {
   // once the hits are known, even if the refinement then fails (as optimize() draws).
   NDTRelocalizeResult relocalize(const NDTFrame* new_frame, const Vector3d& origin, const Vector3d& step, const unsigned count[3],
                                  unsigned top_k);
+  // Several relocalize() calls at once -- the R robots one host thread serves, switched on together or lost together: observably
+  // identical to reqs[i].result = reqs[i].ref->relocalize(reqs[i].cur, origin, step, count, top_k) for i = 0 .. n - 1 in that order
+  // -- the results, the std::rand() stream (a request's tables are drawn in hit order, request by request; a request whose search
+  // fails draws nothing), lastAlignOk(), the refusal of a following update() after a failure, the errors recorded (count, call
+  // site, code; the text too where a request is refused for its own lattice or plan -- after a device failure inside a shared call
+  // every request it failed carries that call's text) -- but consecutive
+  // requests on DIFFERENT resident frames of the calling thread's device context share ONE lattice search call
+  // (ndtpso_map_search_batch, include/ndtpso_hip.h) and ONE refinement launch over all hits of all of them
+  // (ndtpso_map_align_batch).  A frame that appears a second time, as map or as scan, closes the run; a request that cannot be
+  // batched (a null pointer, a frame that is not resident, a scan of another thread's context, frames' own PSOConfigs) is the
+  // member call itself, in its place, so the stream order is kept.
+  static void relocalizeBatch(NDTRelocalizeRequest* reqs, size_t n);
   // Several loadLaser() / update() calls at once: observably identical to the member calls in request order -- `built`, the
   // refusal of an update() after a failed align() with its count (updatesRefused()) and recorded error, the rule for the
   // speculative build, every error recorded as the member call records it -- but consecutive requests that qualify share their

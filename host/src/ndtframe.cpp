@@ -7,6 +7,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <memory>
 
 #include "device.h"
 #include "ndtpso_slam/core.h"
@@ -760,6 +761,162 @@ NDTRelocalizeResult NDTFrame::relocalize(const NDTFrame* new_frame, const Vector
   s_iter = 0;
   recordAlignOutcome(true);
   return NDTRelocalizeResult{pose, jobs[(size_t)best].cost, n_hits, true};
+}
+
+// Several relocalize() calls (see ndtframe.h): the member's own steps per request, with ONE ndtpso_map_search_batch and ONE
+// ndtpso_map_align_batch for a run of requests on different resident frames.
+void NDTFrame::relocalizeBatch(NDTRelocalizeRequest* reqs, size_t n) {
+  if (!reqs) return;
+  ndtpso_host::Ctx* const mine = ndtpso_host::thread_ctx();
+  auto batchable = [&](const NDTRelocalizeRequest& r) {
+    if (!r.ref || !r.cur || align_uses_frame_config()) return false;  // (frames' own PSOConfigs: one cfg per launch)
+    return r.ref->s_resident && r.ref->dev() == mine && r.cur->dev() == mine;
+  };
+  const double first_call[3] = {.1, .1, 3.1415E-3};  // (nextDeviation's)
+  size_t i = 0;
+  while (i < n) {
+    size_t j = i;
+    while (j < n && batchable(reqs[j])) {
+      bool again = false;  // (as alignBatch: per frame the order of the steps is the member calls')
+      for (size_t k = i; k < j && !again; ++k)
+        again = reqs[k].ref == reqs[j].ref || reqs[k].cur == reqs[j].ref || reqs[k].ref == reqs[j].cur;
+      if (again) break;
+      ++j;
+    }
+    if (j - i < 2) {  // relocalize() itself, in its place
+      NDTRelocalizeRequest& r = reqs[i];
+      if (r.ref) {
+        r.result = r.ref->relocalize(r.cur, r.origin, r.step, r.count, r.top_k);
+      } else {
+        ndtpso_host::check(NDTPSO_E_ARG, "relocalize: null argument");
+        r.result = NDTRelocalizeResult{r.origin, 0., 0u, false};
+      }
+      ++i;
+      continue;
+    }
+    ndtpso_host::Use use(mine);
+    const size_t cnt = j - i;
+    // ---- ONE search call over the run ----------------------------------------------------------------------------------------
+    std::vector<int> rc(cnt, NDTPSO_OK);  // per request: what its relocalize() would have been refused with
+    std::vector<const char*> what(cnt, "relocalize");
+    std::vector<std::unique_ptr<DeviceScan>> scans(cnt);
+    std::vector<ndtpso_map*> maps(cnt, nullptr);
+    std::vector<ndtpso_map_search_job> sjobs;
+    std::vector<size_t> sjob_req;
+    std::vector<int> search_job(cnt, -1);  // a request's place in sjobs
+    std::vector<ndtpso_lattice_hit> hits(cnt * NDTPSO_SEARCH_MAX_TOP_K);
+    std::vector<double> unused;
+    for (size_t k = 0; k < cnt; ++k) {
+      NDTRelocalizeRequest& r = reqs[i + k];
+      maps[k] = r.ref->ensureMap();
+      if (!maps[k]) {
+        rc[k] = NDTPSO_E_STATE;
+        what[k] = "relocalize: no device map";
+        continue;
+      }
+      scans[k].reset(new DeviceScan(r.cur, false, unused, "relocalize"));
+      ndtpso_map_search_job job;
+      std::memset(&job, 0, sizeof(job));
+      job.map = maps[k];
+      job.new_points = scans[k]->pts;
+      for (int a = 0; a < 3; ++a) {
+        job.lattice.origin[a] = r.origin[a];
+        job.lattice.step[a] = r.step[a];
+        job.lattice.count[a] = r.count[a];
+      }
+      job.lattice.top_k = r.top_k;
+      job.hits = &hits[k * NDTPSO_SEARCH_MAX_TOP_K];
+      search_job[k] = (int)sjobs.size();
+      sjobs.push_back(job);
+      sjob_req.push_back(k);
+    }
+    std::vector<uint32_t> n_hits(cnt, 0u);
+    if (!sjobs.empty()) {
+      const int rc_call = ndtpso_map_search_batch(ndtpso_host::device(), sjobs.data(), (uint32_t)sjobs.size(), ndtpso_host::score_mode(), nullptr);
+      bool some_job_failed = false;
+      for (const ndtpso_map_search_job& job : sjobs) some_job_failed = some_job_failed || job.rc != NDTPSO_OK;
+      for (size_t q = 0; q < sjobs.size(); ++q) {
+        // (a call refused as a whole failed every request)
+        rc[sjob_req[q]] = (rc_call != NDTPSO_OK && !some_job_failed) ? rc_call : sjobs[q].rc;
+        n_hits[sjob_req[q]] = rc[sjob_req[q]] == NDTPSO_OK ? sjobs[q].n_hits : 0u;
+      }
+    }
+    // ---- the rand() tables, request by request in hit order; ONE refinement launch over all hits ---------------------------------
+    const ndtpso_pso_config abi = to_abi(PSOConfig());  // (what align() passes on, ndtframe.cpp:257)
+    const size_t n_draw = ndtpso_rand_draws(&abi);
+    size_t total = 0;
+    std::vector<size_t> first_job(cnt, 0);
+    for (size_t k = 0; k < cnt; ++k) {
+      first_job[k] = total;
+      total += n_hits[k];
+    }
+    std::vector<ndtpso_map_align_job> jobs(total);
+    std::vector<int32_t> draws(total * n_draw);
+    if (total) std::memset(jobs.data(), 0, total * sizeof(ndtpso_map_align_job));
+    for (size_t k = 0; k < cnt; ++k) {
+      const NDTRelocalizeRequest& r = reqs[i + k];
+      for (uint32_t h = 0; h < n_hits[k]; ++h) {
+        const size_t at = first_job[k] + h;
+        ndtpso_map_align_job& job = jobs[at];
+        job.map = maps[k];
+        job.new_points = scans[k]->pts;
+        ndtpso_host::draw_rand(&draws[at * n_draw], n_draw);  // drawn even if the device call fails (optimize)
+        job.rand_table = &draws[at * n_draw];
+        job.flags = 1u;  // cost wanted
+        for (int a = 0; a < 3; ++a) {
+          job.guess[a] = job.pose[a] = hits[k * NDTPSO_SEARCH_MAX_TOP_K + h].pose[a];
+          job.deviation[a] = r.count[a] > 1 ? r.step[a] / 2. : first_call[a];
+        }
+      }
+    }
+    int rc_align = NDTPSO_OK;
+    bool some_align_failed = false;
+    if (total) {
+      rc_align = ndtpso_map_align_batch(ndtpso_host::device(), jobs.data(), (uint32_t)total, &abi, ndtpso_host::score_mode());
+      for (const ndtpso_map_align_job& job : jobs) some_align_failed = some_align_failed || job.rc != NDTPSO_OK;
+    }
+    // ---- every frame's outcome, in request order ---------------------------------------------------------------------------------
+    for (size_t k = 0; k < cnt; ++k) {
+      NDTRelocalizeRequest& r = reqs[i + k];
+      NDTFrame* f = r.ref;
+      int best = -1;
+      if (rc[k] == NDTPSO_OK) {
+        if (rc_align != NDTPSO_OK && !some_align_failed) {  // (a call refused as a whole failed every job, as in alignBatch)
+          rc[k] = rc_align;
+        } else {
+          for (uint32_t h = 0; h < n_hits[k]; ++h) {
+            const ndtpso_map_align_job& job = jobs[first_job[k] + h];
+            if (job.rc == NDTPSO_OK && (best < 0 || job.cost < jobs[first_job[k] + (size_t)best].cost)) best = (int)h;
+          }
+          if (best < 0) rc[k] = rc_align != NDTPSO_OK ? rc_align : NDTPSO_E_HIP;
+        }
+      }
+      if (rc[k] != NDTPSO_OK) {
+        // The shared search call leaves the context the text of its LAST refusal.  A request refused for its own arguments or plan
+        // gets its own text back from the single call, which refuses it the same way before it enqueues anything.
+        if (search_job[k] >= 0 && (rc[k] == NDTPSO_E_ARG || rc[k] == NDTPSO_E_CAPACITY) && sjobs[(size_t)search_job[k]].rc == rc[k]) {
+          ndtpso_map_search_job& sj = sjobs[(size_t)search_job[k]];
+          uint32_t none = 0;
+          (void)ndtpso_map_search(sj.map, sj.new_points, &sj.lattice, ndtpso_host::score_mode(), sj.hits, &none, nullptr);
+        }
+        ndtpso_host::check(rc[k], what[k]);
+        f->recordAlignOutcome(false);
+        r.result = NDTRelocalizeResult{r.origin, 0., 0u, false};
+        continue;
+      }
+      const ndtpso_map_align_job& won = jobs[first_job[k] + (size_t)best];
+      Vector3d pose(won.pose[0], won.pose[1], won.pose[2]);
+#if TRANSFORM_POSE_AFTER_ALIGN
+      pose -= f->s_trans;
+#endif
+      f->s_prev_pose = pose;
+      f->s_pose_diff = Vector3d::Zero();
+      f->s_iter = 0;
+      f->recordAlignOutcome(true);
+      r.result = NDTRelocalizeResult{pose, won.cost, n_hits[k], true};
+    }
+    i = j;
+  }
 }
 
 // Several loadLaser() calls (see ndtframe.h): the member's own steps per request, with ONE ndtpso_points_load_scans for a run of

@@ -450,6 +450,58 @@ _Static_assert(sizeof(ndtpso_search_stats) == NDTPSO_SEARCH_STATS_BYTES, "ndtpso
 /* (stands for nx * ny * nth calls of cost_function, core.cpp:26-48) */
 int ndtpso_map_search(ndtpso_map *map, ndtpso_points *new_points, const ndtpso_lattice *lattice, int score_mode,
                       ndtpso_lattice_hit *hits, uint32_t *n_hits, ndtpso_search_stats *stats /* may be NULL */);
+/* Several ndtpso_map_search calls of one context in shared launches: the R robots a process relocalizes, or ONE scan against the
+ * M submaps it may have been taken in (the same new_points in M jobs).  The reference has no counterpart, so the contract is the
+ * single call's: job j's hits, n_hits and every field of its stats are bit for bit what
+ *   ndtpso_map_search(jobs[j].map, jobs[j].new_points, &jobs[j].lattice, score_mode, jobs[j].hits, &n_hits, &stats)
+ * returns when called alone, in every score mode (in NDTPSO_SCORE_F32 too: a node is still scored whole by one wave, with the same
+ * trips and the same wave sum), and afterwards every map is in the state the single call leaves it in: a pending speculation
+ * committed, an unbuilt insert built, the header with the host -- once per distinct map, ahead of the launches.
+ *   - Launches: one sweep per kernel kind (score x table plan) present in the call, with the jobs' inputs in a table and the
+ *     workgroups dealt to the jobs in proportion to their items; two selection launches; in the exact mode one collect launch
+ *     (the threshold c32_K + 7e-7 * n_points is formed on the device, by the host's two operations) and one fp64 launch per table
+ *     plan over the jobs' candidate lists.  The number of launches and of waits for the stream does not depend on the number of jobs.
+ *   - Fallbacks are per job: a job whose exact mode sweeps in fp64 (fell_back 1 .. 4) shares one more fp64 sweep and selection
+ *     with the other such jobs of the call and does not drag the rest with it.  A refusal by the start-up check (5) applies to
+ *     every job, as it does to single calls.
+ *   - Errors.  NDTPSO_E_ARG before anything is enqueued (and before any job's out fields are written) for a null pointer (ctx,
+ *     jobs, a job's map, new_points or hits), n_jobs == 0, a map or scan of another context, a bad score mode, or node counts of
+ *     the jobs' (valid) lattices that sum to more than NDTPSO_SEARCH_MAX_NODES: the jobs of a call share the single call's cost
+ *     buffer of 8 bytes x 2^24.  A job whose own lattice the single call would refuse, or whose plan does not fit, gets that
+ *     error in its rc and n_hits = 0; the other jobs complete.  Returns NDTPSO_OK if every job's rc is 0, else the first failing
+ *     job's rc.
+ *   - route: 1 = the shared launches; 0 = ndtpso_map_search's own path: a call of one job, and a job that is the only one of its
+ *     call left with a valid lattice and plan.
+ * stats (may be NULL), counted on the host: launches = kernel launches the searches enqueued (the maps' own builds not counted),
+ * waits = waits for the stream, both of the shared path only; single_jobs = jobs that took route 0. */
+typedef struct {
+  ndtpso_map *map;            /* in: reference frame (may repeat across jobs) */
+  ndtpso_points *new_points;  /* in: loaded scan (may repeat across jobs) */
+  ndtpso_lattice lattice;     /* in */
+  ndtpso_lattice_hit *hits;   /* in: room for lattice.top_k hits; out: the hits */
+  uint32_t n_hits;            /* out */
+  int32_t rc;                 /* out: NDTPSO_OK or this job's error */
+  int32_t route;              /* out: 1 = the shared launches, 0 = ndtpso_map_search's own path */
+  uint32_t reserved;
+  ndtpso_search_stats stats;  /* out */
+} ndtpso_map_search_job;
+typedef struct {
+  uint32_t launches, waits, single_jobs, reserved;
+} ndtpso_search_batch_stats;
+#define NDTPSO_MAP_SEARCH_JOB_BYTES 136
+#define NDTPSO_MAP_SEARCH_JOB_HITS_OFFSET 80
+#define NDTPSO_MAP_SEARCH_JOB_RC_OFFSET 92
+#define NDTPSO_MAP_SEARCH_JOB_STATS_OFFSET 104
+#define NDTPSO_SEARCH_BATCH_STATS_BYTES 16
+#if defined(__cplusplus)
+static_assert(sizeof(ndtpso_map_search_job) == NDTPSO_MAP_SEARCH_JOB_BYTES, "ndtpso_map_search_job layout");
+static_assert(sizeof(ndtpso_search_batch_stats) == NDTPSO_SEARCH_BATCH_STATS_BYTES, "ndtpso_search_batch_stats layout");
+#elif defined(__STDC_VERSION__) && __STDC_VERSION__ >= 201112L
+_Static_assert(sizeof(ndtpso_map_search_job) == NDTPSO_MAP_SEARCH_JOB_BYTES, "ndtpso_map_search_job layout");
+_Static_assert(sizeof(ndtpso_search_batch_stats) == NDTPSO_SEARCH_BATCH_STATS_BYTES, "ndtpso_search_batch_stats layout");
+#endif
+int ndtpso_map_search_batch(ndtpso_ctx *ctx, ndtpso_map_search_job *jobs, uint32_t n_jobs, int score_mode,
+                            ndtpso_search_batch_stats *stats /* may be NULL */);
 int ndtpso_map_get_info(ndtpso_map *map, ndtpso_map_info *info);
 /* created cells in ascending index order (row.reserved = the cell's current window slot) */
 int ndtpso_map_get_cells(ndtpso_map *map, ndtpso_cell_row *rows, uint32_t max_rows, uint32_t *n_rows);

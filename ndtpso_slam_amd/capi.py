@@ -131,6 +131,17 @@ class SearchStats(C.Structure):
                 ("n_candidates", C.c_uint32), ("fell_back", C.c_uint32), ("reserved", C.c_uint32 * 2)]
 
 
+class MapSearchJob(C.Structure):
+    """ndtpso_map_search_job (include/ndtpso_hip.h): one lattice search of ndtpso_map_search_batch"""
+    _fields_ = [("map", C.c_void_p), ("new_points", C.c_void_p), ("lattice", Lattice), ("hits", C.POINTER(LatticeHit)),
+                ("n_hits", C.c_uint32), ("rc", C.c_int32), ("route", C.c_int32), ("reserved", C.c_uint32), ("stats", SearchStats)]
+
+
+class SearchBatchStats(C.Structure):
+    """ndtpso_search_batch_stats: what a ndtpso_map_search_batch call enqueued and waited for, counted on the host"""
+    _fields_ = [("launches", C.c_uint32), ("waits", C.c_uint32), ("single_jobs", C.c_uint32), ("reserved", C.c_uint32)]
+
+
 SEARCH_MAX_TOP_K = 64
 SEARCH_MAX_CANDIDATES = 4096
 # SearchStats.fell_back (NDTPSO_SEARCH_FELL_*): why SCORE_EXACT swept the lattice in fp64
@@ -163,7 +174,7 @@ EXPORTS = [
     "ndtpso_align_pairs_dev", "ndtpso_align_pairs_footprint", "ndtpso_align_pairs_describe",
     "ndtpso_points_create", "ndtpso_points_destroy", "ndtpso_points_load_scan", "ndtpso_points_set", "ndtpso_points_get",
     "ndtpso_map_create", "ndtpso_map_destroy", "ndtpso_map_reset", "ndtpso_map_clear", "ndtpso_map_mark_unbuilt", "ndtpso_map_insert", "ndtpso_map_insert_host",
-    "ndtpso_map_build", "ndtpso_map_speculate_build", "ndtpso_map_align", "ndtpso_map_cost", "ndtpso_map_search", "ndtpso_map_get_info", "ndtpso_map_get_cells", "ndtpso_map_get_points",
+    "ndtpso_map_build", "ndtpso_map_speculate_build", "ndtpso_map_align", "ndtpso_map_cost", "ndtpso_map_search", "ndtpso_map_search_batch", "ndtpso_map_get_info", "ndtpso_map_get_cells", "ndtpso_map_get_points",
     "ndtpso_map_get_occupancy", "ndtpso_map_align_batch", "ndtpso_points_load_scans", "ndtpso_map_update_batch",
     "ndtpso_shard_group_create", "ndtpso_shard_group_destroy", "ndtpso_shard_group_size", "ndtpso_shard_last_error",
     "ndtpso_shard_range", "ndtpso_align_pairs_sharded", "ndtpso_align_pairs_sharded_dev", "ndtpso_shard_last_timing",
@@ -276,6 +287,7 @@ def load(build_if_missing: bool = True):
     L.ndtpso_map_cost.argtypes = [vp, vp, dp, C.c_uint32, C.c_int, dp]
     L.ndtpso_map_search.argtypes = [vp, vp, C.POINTER(Lattice), C.c_int, C.POINTER(LatticeHit), C.POINTER(C.c_uint32),
                                     C.POINTER(SearchStats)]
+    L.ndtpso_map_search_batch.argtypes = [vp, C.POINTER(MapSearchJob), C.c_uint32, C.c_int, C.POINTER(SearchBatchStats)]
     L.ndtpso_map_get_info.argtypes = [vp, C.POINTER(MapInfo)]
     L.ndtpso_map_get_cells.argtypes = [vp, C.POINTER(CellRow), C.c_uint32, up]
     L.ndtpso_map_get_points.argtypes = [vp, C.c_int, dp, C.c_uint64, C.POINTER(C.c_uint64)]
@@ -746,6 +758,38 @@ def update_maps(ctx: "Context", jobs):
     if rc != OK and not (rcs != OK).any():
         ctx._chk(rc)
     return rcs, np.array([j.route for j in arr[:n]], dtype=np.int32)
+
+
+def _search_result(hits, k, st):
+    poses = np.array([h.pose[:] for h in hits[:k]], dtype=np.float64).reshape(k, 3)
+    costs = np.array([h.cost for h in hits[:k]], dtype=np.float64)
+    index = np.array([h.index for h in hits[:k]], dtype=np.uint32)
+    return poses, costs, index, {f: getattr(st, f) for f, _ in SearchStats._fields_ if f != "reserved"}
+
+
+def search_maps(ctx: "Context", jobs, mode=SCORE_EXACT):
+    """ndtpso_map_search_batch: the lattice searches of `jobs` -- (ResidentMap, ResidentScan, origin, step, count, top_k) each, maps
+    and scans free to repeat (one scan against M submaps: the same scan in M jobs) -- in shared launches.  Returns a list with,
+    per job, (poses [K, 3], costs [K], index [K], stats dict, rc, route) -- the first four are what ResidentMap.search returns,
+    route 1: the shared launches, 0: the single call's path -- and the batch statistics as a dict (launches, waits,
+    single_jobs).  Raises only for the call's own errors (bad arguments); a job's failure is its rc."""
+    n = len(jobs)
+    arr = (MapSearchJob * max(n, 1))()
+    keep = []
+    for j, (m, scan, origin, step, count, top_k) in zip(arr, jobs):
+        j.map, j.new_points = m._h, scan._h
+        j.lattice = Lattice((C.c_double * 3)(*[float(v) for v in origin]), (C.c_double * 3)(*[float(v) for v in step]),
+                            (C.c_uint32 * 3)(*[int(v) for v in count]), int(top_k))
+        hits = (LatticeHit * min(max(int(top_k), 1), 1 << 16))()
+        keep.append(hits)
+        j.hits = hits
+    bs = SearchBatchStats()
+    rc = ctx._lib.ndtpso_map_search_batch(ctx._h, arr, n, int(mode), C.byref(bs))
+    rcs = [j.rc for j in arr[:n]]
+    if rc != OK and not any(r != OK for r in rcs):
+        ctx._chk(rc)
+    out = [_search_result(hits, j.n_hits, j.stats) + (j.rc, j.route) for j, hits in zip(arr[:n], keep)]
+    return out, {f: getattr(bs, f) for f, _ in SearchBatchStats._fields_ if f != "reserved"}
 
 
 class ResidentScan:

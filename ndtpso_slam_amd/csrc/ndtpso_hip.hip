@@ -618,6 +618,8 @@ struct ndtpso_ctx {
   size_t jobs_pinned_cap = 0;
   DevBuf jobs_out, jobs_table;
   DevBuf search_costs, search_keys, search_cand;  // ndtpso_map_search: a cost per node, the best-K lists, the exact mode's candidates
+  void* search_pinned = nullptr;      // ndtpso_map_search_batch: the candidates' fp64 costs, written by the rescoring launch itself
+  size_t search_pinned_cap = 0;
   uint32_t jobs_issued = 0;
   bool map_jobs_big_lds = false;      // ndtpso_map_update_batch: k_map_pack_jobs may take the whole LDS (set once per context)
 };
@@ -1110,6 +1112,7 @@ void ndtpso_ctx_destroy(ndtpso_ctx* c) {
   if (c->result_event) (void)hipEventDestroy(c->result_event);
   if (c->result_pinned) (void)hipHostFree(c->result_pinned);
   if (c->jobs_pinned) (void)hipHostFree(c->jobs_pinned);
+  if (c->search_pinned) (void)hipHostFree(c->search_pinned);
   if (c->pairs_fb) (void)hipHostFree(c->pairs_fb);
   if (c->own_stream) (void)hipStreamDestroy(c->own_stream);
   delete c;

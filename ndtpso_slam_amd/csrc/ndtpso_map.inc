@@ -22,6 +22,7 @@
 
 #include "ndtpso_map_jobs.h"
 #include "ndtpso_map_search.h"
+#include "ndtpso_map_search_jobs.h"
 
 // ---- the kernels of the single calls: one map (or one scan) each, the bodies in ndtpso_map_device.inc ---------------------
 __global__ void __launch_bounds__(kInsertThreads)
@@ -200,13 +201,23 @@ int map_clear(ndtpso_map* m) {  // the state of a freshly constructed frame
   return NDTPSO_OK;
 }
 
-int map_fetch_header(ndtpso_map* m) {
+// the header's trip to the host in two halves, so that a call with several maps (ndtpso_map_search_batch) waits once for all of them
+int map_fetch_header_enqueue(ndtpso_map* m) {
   ndtpso_ctx* c = m->ctx;
   HIP_TRY(c, hipMemcpyAsync(&m->host_hdr, m->hdr.p, sizeof(MapHeader), hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(c, hipStreamSynchronize(c->stream));
-  m->known_pts = m->spec ? ~0ull : m->build_pts;  // (a speculative build's header may yet be taken back)
-  if (m->host_hdr.status & kMapPoolExhausted) return fail(c, NDTPSO_E_CAPACITY, "map point pool exhausted");
   return NDTPSO_OK;
+}
+int map_fetch_header_arrived(ndtpso_map* m) {
+  m->known_pts = m->spec ? ~0ull : m->build_pts;  // (a speculative build's header may yet be taken back)
+  if (m->host_hdr.status & kMapPoolExhausted) return fail(m->ctx, NDTPSO_E_CAPACITY, "map point pool exhausted");
+  return NDTPSO_OK;
+}
+
+int map_fetch_header(ndtpso_map* m) {
+  ndtpso_ctx* c = m->ctx;
+  if (int rc = map_fetch_header_enqueue(m)) return rc;
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  return map_fetch_header_arrived(m);
 }
 
 unsigned created_upper(const ndtpso_map* m) {
@@ -914,6 +925,7 @@ int ndtpso_map_cost(ndtpso_map* m, ndtpso_points* pts, const double* poses, uint
 }  // extern "C"
 
 #include "ndtpso_map_search.inc"
+#include "ndtpso_map_search_batch.inc"
 
 extern "C" {
 

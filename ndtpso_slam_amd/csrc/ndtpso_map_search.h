@@ -34,6 +34,15 @@ struct alignas(16) SearchKey {
   uint32_t index, valid;
 };
 
+// The order of the hits: ascending cost by value (-0. and +0. tie), ties by ascending index, a NaN behind every number and NaNs
+// among themselves by index.  A strict total order on (cost, index) for distinct indices, so the best K of a set are the best K
+// of the union of its parts' best K, however the parts were cut.  One text for the single kernels and the job kernels.
+__device__ __forceinline__ bool search_key_less(double a, uint32_t ai, double b, uint32_t bi) {
+  const bool an = a != a, bn = b != b;
+  if (an || bn) return an == bn ? ai < bi : bn;
+  return a < b || (a == b && ai < bi);
+}
+
 constexpr uint32_t kSelectThreads = 1024;
 constexpr uint32_t kSelectMinPerWg = 4096;   // nodes per workgroup of the first selection stage, at least
 constexpr uint32_t kSelectMaxLists = 1024;   // ... and at most this many workgroups (lists the last stage merges)

@@ -54,15 +54,6 @@ k_lattice_sweep(SweepArgs a) {
   }
 }
 
-// The order of the hits: ascending cost by value (-0. and +0. tie), ties by ascending index, a NaN behind every number and NaNs
-// among themselves by index.  A strict total order on (cost, index) for distinct indices, so the best K of a set are the best K
-// of the union of its parts' best K, however the parts were cut.
-__device__ __forceinline__ bool search_key_less(double a, uint32_t ai, double b, uint32_t bi) {
-  const bool an = a != a, bn = b != b;
-  if (an || bn) return an == bn ? ai < bi : bn;
-  return a < b || (a == b && ai < bi);
-}
-
 // Workgroup b: the best k keys of its part [b * per_wg, (b + 1) * per_wg) of the input, in order, into out[b * k ...]: k rounds of
 // "the smallest key behind the last one taken".  KEYS: the input is a list of keys (the merge of the first stage's lists), else
 // costs[] with the position as index.
