@@ -164,6 +164,26 @@ class NDTFrame {
   // request and as scan in another -- closes the run; every other request is the member call itself, in its place.
   static void loadLaserBatch(NDTLoadRequest* reqs, size_t n);
   static void updateBatch(NDTUpdateRequest* reqs, size_t n);
+  // A map outlives its process (not in the reference, whose dumpMap writes a plot nothing reads back).  save() writes this frame
+  // to `path`: the device map's snapshot (ndtpso_map_snapshot, include/ndtpso_hip.h: cells, sliding windows, stored points,
+  // occupancy grid -- everything later results depend on) followed by one section of host state with its own length and
+  // checksum: s_trans, the tracking state align() goes by (previous pose, pose difference, alignments counted, so a loaded
+  // frame's next align() uses the deviation the original's would have used), the frame's NDTPSOConfig, the pose / odometry /
+  // timestamp lists of addPose(), the four extents, `built` and lastAlignOk().  A pending speculative build is put back first,
+  // as by every export; the frame goes on afterwards as if it had not been saved.  The file is written as `path`.tmp and renamed.
+  // load() makes a new frame from such a file in the CALLING thread's device context (the caller deletes it): every later
+  // loadLaser / align / update / relocalize / build / dumpMap on it gives, bit for bit, what it would have given on the original.
+  // The std::rand() stream is the caller's and is not saved: a process that wants the random numbers the original would have
+  // drawn next seeds for them itself (srand(), ndtpso_slam_thread_srand()).
+  // Only resident frames that are maps can be saved: with NDTPSO_RESIDENT=0, on a one-cell per-scan frame (a point list, no map)
+  // and on a frame of 2^21 cells or more (kept on the host's side of the C-ABI, see the constructor) save() returns false and
+  // records the error (ndtpso_slam/status.h); load() returns nullptr and records the error when the file cannot be read, fails
+  // a check (magic, version, constants, counts, checksums of either part) or the device refuses it.  Nothing is left allocated.
+  bool save(const char* path) const;
+  static NDTFrame* load(const char* path);
+  // the pose the frame tracks from: what its last align() or relocalize() returned (zero before the first) -- where a loaded
+  // frame's caller takes up the sequence
+  Vector3d lastPose() const { return s_prev_pose; }
   // new-frame points in the order cost_function visits them (cells, then insertion; core.cpp:33-36)
   void collectPoints(std::vector<double>& xy) const;
   const NDTPSOConfig& config() const { return s_config; }

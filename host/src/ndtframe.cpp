@@ -8,6 +8,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <memory>
+#include <string>
 
 #include "device.h"
 #include "ndtpso_slam/core.h"
@@ -1068,6 +1069,184 @@ void NDTFrame::addPose(double timestamp, const Vector3d& pose, const Vector3d& o
   s_timestamps.push_back(timestamp);
   s_poses.push_back(pose);
   s_odoms.push_back(odom);
+}
+
+// ---- save / load (see ndtframe.h): the C-ABI's map snapshot, followed by one section of host state ------------------------------
+namespace {
+constexpr char kFrameMagic[8] = {'N', 'D', 'T', 'F', 'R', 'A', 'M', 'E'};
+constexpr uint32_t kFrameSectionVersion = 1;
+struct FrameSectionHeader {
+  char magic[8];
+  uint32_t version, reserved;
+  uint64_t bytes, checksum;  // of what follows this header: FNV-1a over its 64-bit words
+};
+struct FrameFixed {  // the section's fixed part; the pose, odometry (3 doubles each) and timestamp lists follow
+  double trans[3], prev_pose[3], pose_diff[3], extent[4];
+  double w, c1, c2, w_dumping;
+  int32_t iterations, population, num_threads, iter;
+  float laser_ignore_epsilon;
+  uint32_t built, last_align_ok, reserved;
+  uint64_t n_poses, n_odoms, n_timestamps;
+};
+static_assert(sizeof(FrameSectionHeader) == 32 && sizeof(FrameFixed) == 192, "frame file layout");
+
+uint64_t fnv1a_words(const unsigned char* p, size_t bytes) {
+  uint64_t h = 0xcbf29ce484222325ull;
+  for (size_t i = 0; i + 8 <= bytes; i += 8) {
+    uint64_t w;
+    std::memcpy(&w, p + i, 8);
+    h = (h ^ w) * 0x100000001b3ull;
+  }
+  return h;
+}
+bool save_refused(int rc, const char* what) {
+  ndtpso_host::check(rc, what);
+  return false;
+}
+NDTFrame* load_refused(int rc, const char* what) {
+  ndtpso_host::check(rc, what);
+  return nullptr;
+}
+}  // namespace
+
+bool NDTFrame::save(const char* path) const {
+  if (!path) return save_refused(NDTPSO_E_ARG, "save: null path");
+  if (!s_resident)
+    return save_refused(NDTPSO_E_STATE, numOfCells >= (1u << 21) ? "save: a frame of 2^21 cells or more is kept on the host's side and cannot be saved"
+                                                                  : "save: the frame is not resident");
+  if (d_scan_ && !d_map_) return save_refused(NDTPSO_E_STATE, "save: a one-cell scan frame holds no map");
+  ndtpso_host::Use use(dev());
+  ndtpso_map* m = const_cast<NDTFrame*>(this)->ensureMap();  // (a frame nothing was done to yet: an empty map)
+  if (!m) return save_refused(NDTPSO_E_STATE, "save: no device map");
+  uint64_t blob_bytes = 0;
+  if (!ndtpso_host::check(ndtpso_map_snapshot_size(m, &blob_bytes), "save")) return false;
+  FrameFixed fx;
+  std::memset(&fx, 0, sizeof(fx));
+  for (int a = 0; a < 3; ++a) {
+    fx.trans[a] = s_trans[a];
+    fx.prev_pose[a] = s_prev_pose[a];
+    fx.pose_diff[a] = s_pose_diff[a];
+  }
+  fx.extent[0] = s_x_min;
+  fx.extent[1] = s_x_max;
+  fx.extent[2] = s_y_min;
+  fx.extent[3] = s_y_max;
+  fx.w = s_config.psoConfig.coeff.w;
+  fx.c1 = s_config.psoConfig.coeff.c1;
+  fx.c2 = s_config.psoConfig.coeff.c2;
+  fx.w_dumping = s_config.psoConfig.coeff.w_dumping;
+  fx.iterations = s_config.psoConfig.iterations;
+  fx.population = s_config.psoConfig.populationSize;
+  fx.num_threads = s_config.psoConfig.num_threads;
+  fx.iter = s_iter;
+  fx.laser_ignore_epsilon = s_config.laserIgnoreEpsilon;
+  fx.built = built ? 1u : 0u;
+  fx.last_align_ok = s_last_align_ok ? 1u : 0u;
+  fx.n_poses = s_poses.size();
+  fx.n_odoms = s_odoms.size();
+  fx.n_timestamps = s_timestamps.size();
+  const size_t section = sizeof(fx) + 24 * (s_poses.size() + s_odoms.size()) + 8 * s_timestamps.size();
+  std::vector<unsigned char> file((size_t)blob_bytes + sizeof(FrameSectionHeader) + section);
+  if (!ndtpso_host::check(ndtpso_map_snapshot(m, file.data(), blob_bytes, &blob_bytes), "save")) return false;
+  unsigned char* at = file.data() + blob_bytes + sizeof(FrameSectionHeader);
+  std::memcpy(at, &fx, sizeof(fx));
+  at += sizeof(fx);
+  for (const vector<Vector3d>* list : {&s_poses, &s_odoms})
+    for (const Vector3d& v : *list) {
+      const double xyz[3] = {v.x(), v.y(), v.z()};
+      std::memcpy(at, xyz, 24);
+      at += 24;
+    }
+  if (!s_timestamps.empty()) std::memcpy(at, s_timestamps.data(), 8 * s_timestamps.size());
+  FrameSectionHeader sh;
+  std::memset(&sh, 0, sizeof(sh));
+  std::memcpy(sh.magic, kFrameMagic, 8);
+  sh.version = kFrameSectionVersion;
+  sh.bytes = section;
+  sh.checksum = fnv1a_words(file.data() + blob_bytes + sizeof(sh), section);
+  std::memcpy(file.data() + blob_bytes, &sh, sizeof(sh));
+  // written beside the target and renamed over it: a reader never sees half a file
+  const std::string tmp = std::string(path) + ".tmp";
+  FILE* f = std::fopen(tmp.c_str(), "wb");
+  if (!f) return save_refused(NDTPSO_E_ARG, "save: cannot create the file");
+  const bool written = std::fwrite(file.data(), 1, file.size(), f) == file.size();
+  const bool closed = std::fclose(f) == 0;
+  if (!written || !closed || std::rename(tmp.c_str(), path) != 0) {
+    std::remove(tmp.c_str());
+    return save_refused(NDTPSO_E_ARG, "save: cannot write the file");
+  }
+  return true;
+}
+
+NDTFrame* NDTFrame::load(const char* path) {
+  if (!path) return load_refused(NDTPSO_E_ARG, "load: null path");
+  if (!ndtpso_host::resident_default()) return load_refused(NDTPSO_E_STATE, "load: frames are not resident (NDTPSO_RESIDENT=0)");
+  std::vector<unsigned char> file;
+  {
+    FILE* f = std::fopen(path, "rb");
+    if (!f) return load_refused(NDTPSO_E_ARG, "load: cannot open the file");
+    unsigned char buf[1 << 16];
+    for (size_t n; (n = std::fread(buf, 1, sizeof(buf), f)) > 0;) file.insert(file.end(), buf, buf + n);
+    std::fclose(f);
+  }
+  uint64_t blob_bytes = 0;
+  if (file.size() >= NDTPSO_SNAPSHOT_BYTES_OFFSET + 8) std::memcpy(&blob_bytes, file.data() + NDTPSO_SNAPSHOT_BYTES_OFFSET, 8);
+  ndtpso_snapshot_info info;
+  if (blob_bytes > file.size() || ndtpso_snapshot_describe(file.data(), blob_bytes, &info) != NDTPSO_OK)
+    return load_refused(NDTPSO_E_ARG, "load: the file does not begin with a valid map snapshot");
+  FrameSectionHeader sh;
+  FrameFixed fx;
+  if (file.size() - blob_bytes < sizeof(sh) + sizeof(fx)) return load_refused(NDTPSO_E_ARG, "load: the host section is missing");
+  std::memcpy(&sh, file.data() + blob_bytes, sizeof(sh));
+  const unsigned char* section = file.data() + blob_bytes + sizeof(sh);
+  if (std::memcmp(sh.magic, kFrameMagic, 8) != 0 || sh.version != kFrameSectionVersion || sh.bytes != file.size() - blob_bytes - sizeof(sh) ||
+      sh.checksum != fnv1a_words(section, (size_t)sh.bytes))
+    return load_refused(NDTPSO_E_ARG, "load: bad host section (magic, version, length or checksum)");
+  std::memcpy(&fx, section, sizeof(fx));
+  const uint64_t lists = (sh.bytes - sizeof(fx)) / 8;
+  if (fx.n_poses > lists || fx.n_odoms > lists || fx.n_timestamps > lists ||
+      sh.bytes != sizeof(fx) + 24 * (fx.n_poses + fx.n_odoms) + 8 * fx.n_timestamps)
+    return load_refused(NDTPSO_E_ARG, "load: bad host section (list lengths)");
+  NDTPSOConfig cfg;
+  cfg.psoConfig.iterations = fx.iterations;
+  cfg.psoConfig.populationSize = fx.population;
+  cfg.psoConfig.num_threads = fx.num_threads;
+  cfg.psoConfig.coeff.w = fx.w;
+  cfg.psoConfig.coeff.c1 = fx.c1;
+  cfg.psoConfig.coeff.c2 = fx.c2;
+  cfg.psoConfig.coeff.w_dumping = fx.w_dumping;
+  cfg.laserIgnoreEpsilon = fx.laser_ignore_epsilon;
+  std::unique_ptr<NDTFrame> frame(new NDTFrame(Vector3d(fx.trans[0], fx.trans[1], fx.trans[2]), info.grid.width, info.grid.height,
+                                               info.grid.cell_side, true, cfg, info.og_cell_size));
+  if (!frame->s_resident) return load_refused(NDTPSO_E_STATE, "load: the frame is not resident");
+  ndtpso_host::Use use(frame->dev());
+  // (the pool ndtpso_map_create would have got, or twice what the saved map fills if that is more)
+  const uint64_t pool = std::max<uint64_t>(map_pool_bytes(frame->numOfCells), 2 * 512 * info.n_chunks);
+  if (!ndtpso_host::check(ndtpso_map_restore(ndtpso_host::device(), file.data(), blob_bytes, pool, &frame->d_map_), "load")) {
+    frame->d_map_ = nullptr;
+    return nullptr;
+  }
+  frame->s_prev_pose = Vector3d(fx.prev_pose[0], fx.prev_pose[1], fx.prev_pose[2]);
+  frame->s_pose_diff = Vector3d(fx.pose_diff[0], fx.pose_diff[1], fx.pose_diff[2]);
+  frame->s_x_min = fx.extent[0];
+  frame->s_x_max = fx.extent[1];
+  frame->s_y_min = fx.extent[2];
+  frame->s_y_max = fx.extent[3];
+  frame->s_iter = fx.iter;
+  frame->built = fx.built != 0;
+  frame->s_last_align_ok = fx.last_align_ok != 0;
+  const unsigned char* at = section + sizeof(fx);
+  for (vector<Vector3d>* list : {&frame->s_poses, &frame->s_odoms}) {
+    const uint64_t n = list == &frame->s_poses ? fx.n_poses : fx.n_odoms;
+    for (uint64_t k = 0; k < n; ++k, at += 24) {
+      double xyz[3];
+      std::memcpy(xyz, at, 24);
+      list->push_back(Vector3d(xyz[0], xyz[1], xyz[2]));
+    }
+  }
+  frame->s_timestamps.resize((size_t)fx.n_timestamps);
+  if (fx.n_timestamps) std::memcpy(frame->s_timestamps.data(), at, 8 * (size_t)fx.n_timestamps);
+  return frame.release();
 }
 
 void NDTFrame::resetCells() {

@@ -512,6 +512,48 @@ int ndtpso_map_get_points(ndtpso_map *map, int slot0_only, double *xy, uint64_t 
 int ndtpso_map_get_occupancy(ndtpso_map *map, int8_t *og, uint64_t og_bytes, uint32_t *og_width, uint32_t *og_height,
                              uint32_t extent[4]);
 
+/* ---- a resident map saved to a blob and restored bit for bit ---------------------------------------------------
+ * The reference has no counterpart (dumpMap, ndtframe.cpp:314-328, writes points for a plot; nothing reads them back).  A
+ * snapshot is a compact, deterministic, versioned image of everything about a map that is primary state: the created cells in
+ * creation order, of each the cell record and the window slots in use (partial sums, covariances, counts, the stored points in
+ * insertion order), the header, the occupancy keys inside the rasterised box, and `built`, the build number and the host's
+ * bounds.  The alignment table is derived and is packed again by the restore (of a map that is not built, the header's table
+ * fields -- n_built, n_words, the built cells' box -- describe a table that is no longer current and are saved as zero: the
+ * next build writes them).  A restored map behaves under every later call
+ * exactly as the original would have: cells, points, occupancy, costs, alignments and searches are bit for bit the original's,
+ * now and after any number of further inserts and builds.  The same map state gives the same bytes, and
+ * snapshot(restore(blob)) == blob.  Size is proportional to content, never to the frame:
+ *   bytes <= 4096 + 192 * n_created + 80 * n_slots_used + 528 * n_chunks + 8 * og_box_entries.
+ * Format 1: little-endian, 16-byte aligned sections, 64-bit sizes and offsets, magic, version, the constants it was made with
+ * (NDTPSO_WINDOW_SIZE, NDTPSO_MAX_POINTS_PER_CELL, chunk size, cell record size), FNV-1a checksums of header and body. */
+typedef struct {
+  uint32_t version, n_created, n_built, built; /* format; created cells; cells of the table (0 unless built); NDTFrame::built */
+  uint64_t n_slots_used, n_chunks, n_points_stored, og_box_entries, bytes;
+  ndtpso_grid grid;
+  double og_cell_size;
+} ndtpso_snapshot_info;
+#define NDTPSO_SNAPSHOT_INFO_BYTES 80
+#define NDTPSO_SNAPSHOT_BYTES_OFFSET 32 /* format 1: the blob's own size, a little-endian uint64 at this byte (a blob inside a larger file) */
+#if defined(__cplusplus)
+static_assert(sizeof(ndtpso_snapshot_info) == NDTPSO_SNAPSHOT_INFO_BYTES, "ndtpso_snapshot_info layout");
+#elif defined(__STDC_VERSION__) && __STDC_VERSION__ >= 201112L
+_Static_assert(sizeof(ndtpso_snapshot_info) == NDTPSO_SNAPSHOT_INFO_BYTES, "ndtpso_snapshot_info layout");
+#endif
+/* The size ndtpso_map_snapshot needs now.  Settles the map as the exports do (a pending speculative build is put back first;
+ * NDTFrame::built stays what it is: a map with points inserted since its last build is saved unbuilt).  Synchronous. */
+int ndtpso_map_snapshot_size(ndtpso_map *map, uint64_t *bytes);
+/* Writes the blob; *bytes = its size.  capacity too small: NDTPSO_E_CAPACITY, *bytes = the size needed, nothing written.  A map
+ * whose point pool has run out (ndtpso_map_info.status bit 0) has lost points and is refused with NDTPSO_E_CAPACITY.  Synchronous. */
+int ndtpso_map_snapshot(ndtpso_map *map, void *blob, uint64_t capacity, uint64_t *bytes);
+/* A new map of `ctx` -- any context: another thread's or another device's, which makes this the way to clone a map -- from a
+ * blob.  pool_bytes as ndtpso_map_create's.  Everything is checked before device memory is allocated: magic, version, constants,
+ * grid, counts (n_chunks == sum of ceil(slot_len / 32)), section bounds against `bytes`, checksums.  A mismatch returns
+ * NDTPSO_E_ARG with a message that names the field, a pool too small for the blob's chunks NDTPSO_E_CAPACITY; *out is NULL then
+ * and nothing stays allocated.  Synchronous. */
+int ndtpso_map_restore(ndtpso_ctx *ctx, const void *blob, uint64_t bytes, uint64_t pool_bytes, ndtpso_map **out);
+/* What a blob holds, after the same checks (NDTPSO_E_ARG if one fails).  Host only: no context, no device. */
+int ndtpso_snapshot_describe(const void *blob, uint64_t bytes, ndtpso_snapshot_info *info);
+
 /* ---- one alignment on several compute units --------------------------
  * ndtpso_align, ndtpso_map_align and small batches of ndtpso_align_pairs* spread an alignment over K workgroups (each
  * keeps the table, the points and the whole swarm and runs the identical control flow; the cost evaluations of a round

@@ -96,6 +96,13 @@ class MapInfo(C.Structure):
                 ("pool_bump", C.c_int32), ("pool_free", C.c_int32), ("n_points", C.c_uint64)]
 
 
+class SnapshotInfo(C.Structure):
+    """ndtpso_snapshot_info (include/ndtpso_hip.h): what a map snapshot holds"""
+    _fields_ = [("version", C.c_uint32), ("n_created", C.c_uint32), ("n_built", C.c_uint32), ("built", C.c_uint32),
+                ("n_slots_used", C.c_uint64), ("n_chunks", C.c_uint64), ("n_points_stored", C.c_uint64),
+                ("og_box_entries", C.c_uint64), ("bytes", C.c_uint64), ("grid", Grid), ("og_cell_size", C.c_double)]
+
+
 class MapAlignJob(C.Structure):
     """ndtpso_map_align_job (include/ndtpso_hip.h): one alignment of ndtpso_map_align_batch"""
     _fields_ = [("map", C.c_void_p), ("new_points", C.c_void_p), ("guess", C.c_double * 3), ("deviation", C.c_double * 3),
@@ -175,7 +182,8 @@ EXPORTS = [
     "ndtpso_points_create", "ndtpso_points_destroy", "ndtpso_points_load_scan", "ndtpso_points_set", "ndtpso_points_get",
     "ndtpso_map_create", "ndtpso_map_destroy", "ndtpso_map_reset", "ndtpso_map_clear", "ndtpso_map_mark_unbuilt", "ndtpso_map_insert", "ndtpso_map_insert_host",
     "ndtpso_map_build", "ndtpso_map_speculate_build", "ndtpso_map_align", "ndtpso_map_cost", "ndtpso_map_search", "ndtpso_map_search_batch", "ndtpso_map_get_info", "ndtpso_map_get_cells", "ndtpso_map_get_points",
-    "ndtpso_map_get_occupancy", "ndtpso_map_align_batch", "ndtpso_points_load_scans", "ndtpso_map_update_batch",
+    "ndtpso_map_get_occupancy", "ndtpso_map_snapshot_size", "ndtpso_map_snapshot", "ndtpso_map_restore", "ndtpso_snapshot_describe",
+    "ndtpso_map_align_batch", "ndtpso_points_load_scans", "ndtpso_map_update_batch",
     "ndtpso_shard_group_create", "ndtpso_shard_group_destroy", "ndtpso_shard_group_size", "ndtpso_shard_last_error",
     "ndtpso_shard_range", "ndtpso_align_pairs_sharded", "ndtpso_align_pairs_sharded_dev", "ndtpso_shard_last_timing",
     "ndtpso_shard_gathered", "ndtpso_shard_group_describe", "ndtpso_shard_verify_gather",
@@ -292,6 +300,10 @@ def load(build_if_missing: bool = True):
     L.ndtpso_map_get_cells.argtypes = [vp, C.POINTER(CellRow), C.c_uint32, up]
     L.ndtpso_map_get_points.argtypes = [vp, C.c_int, dp, C.c_uint64, C.POINTER(C.c_uint64)]
     L.ndtpso_map_get_occupancy.argtypes = [vp, C.POINTER(C.c_int8), C.c_uint64, up, up, up]
+    L.ndtpso_map_snapshot_size.argtypes = [vp, C.POINTER(C.c_uint64)]
+    L.ndtpso_map_snapshot.argtypes = [vp, vp, C.c_uint64, C.POINTER(C.c_uint64)]
+    L.ndtpso_map_restore.argtypes = [vp, vp, C.c_uint64, C.c_uint64, C.POINTER(vp)]
+    L.ndtpso_snapshot_describe.argtypes = [vp, C.c_uint64, C.POINTER(SnapshotInfo)]
     L.ndtpso_shard_group_create.argtypes = [ip, C.c_int, C.POINTER(vp)]
     L.ndtpso_shard_group_destroy.argtypes = [vp]
     L.ndtpso_shard_group_destroy.restype = None
@@ -680,6 +692,18 @@ def align_pairs_describe(geom: ScanGeom, grid: Grid, cfg: PSOConfig, mode=SCORE_
     return rc, {k: getattr(pl, k) for k, _ in PairsPlan._fields_}
 
 
+def snapshot_describe(blob) -> dict:
+    """ndtpso_snapshot_describe: what a map snapshot holds, after the checks a restore makes.  Host only: needs no Context."""
+    blob = bytes(blob)
+    info = SnapshotInfo()
+    rc = load().ndtpso_snapshot_describe(blob, len(blob), C.byref(info))
+    if rc != 0:
+        raise NdtpsoError(rc, "not a valid map snapshot")
+    d = {k: getattr(info, k) for k, _ in SnapshotInfo._fields_ if k != "grid"}
+    d["grid"] = (info.grid.width, info.grid.height, info.grid.cell_side)
+    return d
+
+
 def align_maps(ctx: "Context", jobs, cfg: PSOConfig, mode=SCORE_F32):
     """ndtpso_map_align_batch: the alignments of `jobs` -- (ResidentMap, ResidentScan, guess, deviation, seed | rand_table) each,
     a rand table being anything but an integer -- in one launch.  Returns poses [J, 3], costs [J], a dict of statistics arrays
@@ -855,6 +879,28 @@ class ResidentMap:
             self.close()
         except Exception:
             pass
+
+    def snapshot(self) -> bytes:
+        """ndtpso_map_snapshot: everything about the map that is primary state, as one deterministic blob"""
+        n = C.c_uint64()
+        self._ctx._chk(self._lib.ndtpso_map_snapshot_size(self._h, C.byref(n)))
+        buf = C.create_string_buffer(max(n.value, 1))
+        self._ctx._chk(self._lib.ndtpso_map_snapshot(self._h, buf, n.value, C.byref(n)))
+        return buf.raw[:n.value]
+
+    @classmethod
+    def restore(cls, ctx: Context, blob, pool_bytes=0) -> "ResidentMap":
+        """ndtpso_map_restore: a new map of `ctx` (any context: this is how a map is cloned) that behaves as the saved one would"""
+        blob = bytes(blob)
+        h = C.c_void_p()
+        ctx._chk(ctx._lib.ndtpso_map_restore(ctx._h, blob, len(blob), int(pool_bytes), C.byref(h)))
+        info = snapshot_describe(blob)
+        m = cls.__new__(cls)
+        m._ctx = ctx
+        m._lib = ctx._lib
+        m.grid = Grid(*info["grid"])
+        m._h = h
+        return m
 
     def reset(self):
         """NDTFrame::resetCells"""

@@ -23,6 +23,7 @@
 #include "ndtpso_map_jobs.h"
 #include "ndtpso_map_search.h"
 #include "ndtpso_map_search_jobs.h"
+#include "ndtpso_map_snapshot.h"
 
 // ---- the kernels of the single calls: one map (or one scan) each, the bodies in ndtpso_map_device.inc ---------------------
 __global__ void __launch_bounds__(kInsertThreads)
@@ -143,6 +144,7 @@ struct ndtpso_map {
   MapP p{};
   DevBuf cell, win_sum, win_cov, win_count, slot_head, slot_tail, slot_len, chunk_pts, chunk_next, free_list, created,
       hdr, image, og_key, stage;
+  DevBuf snap, snap_idx;       // ndtpso_map_snapshot / ndtpso_map_restore: the staged blob and its index, for the length of a call
   double og_cell_size = 0.;
   uint32_t og_width = 0, og_height = 0, og_count = 0;
   int n_words_max = 0;
@@ -170,7 +172,7 @@ namespace {
 void map_release(ndtpso_map* m) {
   for (DevBuf* b : {&m->cell, &m->win_sum, &m->win_cov, &m->win_count, &m->slot_head, &m->slot_tail, &m->slot_len,
                     &m->chunk_pts, &m->chunk_next, &m->free_list, &m->created, &m->hdr, &m->image, &m->og_key, &m->stage,
-                    &m->undo})
+                    &m->undo, &m->snap, &m->snap_idx})
     b->release();
   if (m->spec_hdr) (void)hipHostFree(m->spec_hdr);
   m->spec_hdr = nullptr;
@@ -1023,3 +1025,5 @@ int ndtpso_map_get_occupancy(ndtpso_map* m, int8_t* og, uint64_t og_bytes, uint3
 }
 
 }  // extern "C"
+
+#include "ndtpso_map_snapshot.inc"
