@@ -60,6 +60,29 @@ struct NDTRelocalizeRequest {
   NDTRelocalizeResult result;  // out
 };
 
+// What NDTFrame::curvature returns (not in the reference): the score at a pose with its gradient and Hessian (xx, xy, xth, yy, yth,
+// thth), the pose covariance they stand for -- the plain inverse Hessian, row-major: a relative measure, the caller owns the
+// scale factor for their sensor's noise -- and the principal axes of its translational block.  definite: the Hessian is
+// positive definite (else covariance and the xy fields are zeros: a saddle, no overlap, a NaN).  ok: the device did it (false:
+// everything zero, the error is recorded, status.h).
+struct NDTCurvature {
+  double cost;
+  Vector3d gradient;
+  double hessian[6];
+  double covariance[9];
+  double xy_major, xy_minor, xy_angle;
+  unsigned n_points, n_hit;
+  bool definite, ok;
+};
+
+// One request of NDTFrame::curvatureBatch (not in the reference): result = ref->curvature(pose, cur).
+struct NDTCurvatureRequest {
+  NDTFrame* ref;
+  const NDTFrame* cur;
+  Vector3d pose;
+  NDTCurvature result;  // out
+};
+
 // One request of NDTFrame::loadLaserBatch (not in the reference): frame->loadLaser(*laser_data, min_angle, angle_increment, max_range).
 struct NDTLoadRequest {
   NDTFrame* frame;
@@ -154,6 +177,19 @@ class NDTFrame {
   // batched (a null pointer, a frame that is not resident, a scan of another thread's context, frames' own PSOConfigs) is the
   // member call itself, in its place, so the stream order is kept.
   static void relocalizeBatch(NDTRelocalizeRequest* reqs, size_t n);
+  // How well is `pose` constrained: cost_function (core.cpp:26-48) with normalDistribution (ndtcell.cpp:70-78) differentiated once
+  // and twice by the pose, on the device in fp64 (ndtpso_map_curvature, include/ndtpso_hip.h), and the inverse Hessian as pose
+  // covariance.  `pose` is in the convention align() returns and cost() takes; cost is cost(pose, new_frame) bit for bit.  The
+  // conventions are cost()'s: a resident frame, the scan as a device-resident point list (a scan of another thread's context
+  // goes through the host), the frame built first if need be -- `built` is the only state that changes.  It is an observer: it
+  // draws nothing from std::rand() and leaves the tracking state, lastAlignOk() and the refusal of update() as they are.  On a
+  // frame that is not resident, or when a device call fails, the result is all zeros with ok = false and the error is recorded
+  // (ndtpso_slam/status.h); it never aborts.
+  NDTCurvature curvature(const Vector3d& pose, const NDTFrame* new_frame);
+  // Several curvature() calls at once: observably the member calls in request order, but consecutive requests on resident frames
+  // of the calling thread's device context go out as ONE ndtpso_map_curvature_batch.  Maps and scans may repeat freely (nothing
+  // depends on an earlier result); a request that cannot join takes the member call, in its place.
+  static void curvatureBatch(NDTCurvatureRequest* reqs, size_t n);
   // Several loadLaser() / update() calls at once: observably identical to the member calls in request order -- `built`, the
   // refusal of an update() after a failed align() with its count (updatesRefused()) and recorded error, the rule for the
   // speculative build, every error recorded as the member call records it -- but consecutive requests that qualify share their

@@ -7,6 +7,8 @@
 //          [pixels_per_metre]]]
 //   NODE_REPLAY_PACE_HZ=f in the environment delivers the scans at f Hz like a sensor would (the time a scan takes is
 //   then the latency a robot sees, with whatever the library does between scans off the clock)
+//   NODE_REPLAY_CURVATURE=1 calls ref_frame->curvature() at the pose every align() returns, as a node that fills its message's
+//   covariance would (its time is reported on its own; poses and the rand() stream are the same with and without it)
 // With a dump prefix the shutdown export of the node (:141-172) runs too: a one-cell global map collects every 10th
 // scan (SAVE_DATA_TO_FILE_EACH_NUM_ITERS, ndtpso_slam_node.hpp:18; NODE_REPLAY_SAVE_EACH=n overrides) and every
 // pose and is dumped as <prefix>.{pose.csv,map.csv,gnuplot,png}; the reference frame (with its occupancy grid) as
@@ -59,6 +61,8 @@ int main(int argc, char** argv) {
   auto t_prev_end = std::chrono::steady_clock::now();
   const double pace_hz = std::getenv("NODE_REPLAY_PACE_HZ") ? std::atof(std::getenv("NODE_REPLAY_PACE_HZ")) : 0.;
   auto next_scan = std::chrono::steady_clock::now();
+  const bool with_curvature = std::getenv("NODE_REPLAY_CURVATURE") && std::getenv("NODE_REPLAY_CURVATURE")[0] == '1';
+  double curvature_s = 0.;
   for (int k = 0; k < n_scans; ++k) {
     if (std::fread(ranges.data(), 4, (size_t)n_beams, f) != (size_t)n_beams) return 2;
     if (pace_hz > 0.) {
@@ -73,6 +77,11 @@ int main(int argc, char** argv) {
     else
       current_pose = ref_frame->align(previous_pose, current_frame);           // :194
     previous_pose = current_pose;
+    if (with_curvature && !first_iteration) {
+      const auto tc = std::chrono::steady_clock::now();
+      (void)ref_frame->curvature(current_pose, current_frame);
+      curvature_s += std::chrono::duration<double>(std::chrono::steady_clock::now() - tc).count();
+    }
     const auto t2 = std::chrono::steady_clock::now();
     ref_frame->update(current_pose, current_frame);                            // :198
     const auto t3 = std::chrono::steady_clock::now();
@@ -100,6 +109,8 @@ int main(int argc, char** argv) {
   if (n_scans > 1 && std::getenv("NODE_REPLAY_TIMING"))
     std::fprintf(stderr, "per scan (us): loadLaser %.1f  align %.1f  update %.1f  between scans %.1f\n", 1e6 * part_s[0] / (n_scans - 1),
                  1e6 * part_s[1] / (n_scans - 1), 1e6 * part_s[2] / (n_scans - 1), 1e6 * part_s[3] / (n_scans - 1));
+  if (n_scans > 1 && with_curvature && std::getenv("NODE_REPLAY_TIMING"))
+    std::fprintf(stderr, "per scan (us): curvature %.1f (inside align's figure)\n", 1e6 * curvature_s / (n_scans - 1));
   if (n_scans > 1)  // the node's own metric ("matching rate", ndtpso_slam_node.cpp:239): loadLaser + align + update per scan
     std::fprintf(stderr, "matching rate: %.1f Hz (%.3f ms per scan)\n", (n_scans - 1) / busy_s, 1e3 * busy_s / (n_scans - 1));
   if (dump_prefix) {  // :141-172

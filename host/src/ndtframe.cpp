@@ -920,6 +920,137 @@ void NDTFrame::relocalizeBatch(NDTRelocalizeRequest* reqs, size_t n) {
   }
 }
 
+namespace {
+// a device curvature as the drop-in returns it, with the covariance it stands for (host arithmetic, no device)
+NDTCurvature curvature_result(const ndtpso_curvature& c) {
+  NDTCurvature r;
+  std::memset(static_cast<void*>(&r), 0, sizeof(r));
+  r.cost = c.cost;
+  r.gradient = Vector3d(c.gradient[0], c.gradient[1], c.gradient[2]);
+  for (int i = 0; i < 6; ++i) r.hessian[i] = c.hessian[i];
+  r.n_points = c.n_points;
+  r.n_hit = c.n_hit;
+  ndtpso_pose_covariance pc;
+  (void)ndtpso_curvature_covariance(&c, &pc);  // (no null pointer here: it cannot fail)
+  for (int i = 0; i < 9; ++i) r.covariance[i] = pc.cov[i];
+  r.xy_major = pc.xy_major;
+  r.xy_minor = pc.xy_minor;
+  r.xy_angle = pc.xy_angle;
+  r.definite = pc.definite != 0;
+  r.ok = true;
+  return r;
+}
+NDTCurvature curvature_failed() {
+  NDTCurvature r;
+  std::memset(static_cast<void*>(&r), 0, sizeof(r));
+  r.gradient = Vector3d::Zero();
+  return r;
+}
+}  // namespace
+
+// Gradient, Hessian and covariance of the score at a pose (see ndtframe.h): cost()'s conventions, an observer.
+NDTCurvature NDTFrame::curvature(const Vector3d& pose, const NDTFrame* new_frame) {
+  if (!new_frame) {
+    ndtpso_host::check(NDTPSO_E_ARG, "curvature: null argument");
+    return curvature_failed();
+  }
+  if (!s_resident) {
+    ndtpso_host::check(NDTPSO_E_STATE, "curvature: the frame is not resident");
+    return curvature_failed();
+  }
+  std::vector<double> foreign;
+  const bool is_foreign = new_frame->dev() != dev();
+  if (is_foreign) new_frame->collectPoints(foreign);
+  ndtpso_host::Use use(dev());
+  ndtpso_map* m = ensureMap();
+  if (!m) {
+    ndtpso_host::check(NDTPSO_E_STATE, "curvature: no device map");
+    return curvature_failed();
+  }
+  const DeviceScan scan(new_frame, is_foreign, foreign, "curvature");
+  const double p[3] = {pose.x(), pose.y(), pose.z()};
+  ndtpso_curvature c;
+  std::memset(&c, 0, sizeof(c));
+  if (!ndtpso_host::check(ndtpso_map_curvature(m, scan.pts, p, 1, &c), "curvature")) return curvature_failed();
+  built = true;  // (the call built first if need be, as cost()'s)
+  return curvature_result(c);
+}
+
+// Several curvature() calls (see ndtframe.h): ONE ndtpso_map_curvature_batch for a run of requests on resident frames of the
+// calling thread's context.
+void NDTFrame::curvatureBatch(NDTCurvatureRequest* reqs, size_t n) {
+  if (!reqs) return;
+  ndtpso_host::Ctx* const mine = ndtpso_host::thread_ctx();
+  auto batchable = [&](const NDTCurvatureRequest& r) {
+    return r.ref && r.cur && r.ref->s_resident && r.ref->dev() == mine && r.cur->dev() == mine;
+  };
+  size_t i = 0;
+  while (i < n) {
+    size_t j = i;
+    while (j < n && batchable(reqs[j])) ++j;
+    if (j - i < 2) {  // curvature() itself, in its place
+      NDTCurvatureRequest& r = reqs[i];
+      if (r.ref) {
+        r.result = r.ref->curvature(r.pose, r.cur);
+      } else {
+        ndtpso_host::check(NDTPSO_E_ARG, "curvature: null argument");
+        r.result = curvature_failed();
+      }
+      ++i;
+      continue;
+    }
+    ndtpso_host::Use use(mine);
+    const size_t cnt = j - i;
+    std::vector<int> rc(cnt, NDTPSO_OK);
+    std::vector<const char*> what(cnt, "curvature");
+    std::vector<std::unique_ptr<DeviceScan>> scans(cnt);
+    std::vector<ndtpso_map_curvature_job> jobs;
+    std::vector<size_t> job_req;
+    std::vector<double> poses(3 * cnt);
+    std::vector<ndtpso_curvature> out(cnt);
+    std::memset(out.data(), 0, cnt * sizeof(ndtpso_curvature));
+    std::vector<double> unused;
+    for (size_t k = 0; k < cnt; ++k) {
+      NDTCurvatureRequest& r = reqs[i + k];
+      ndtpso_map* m = r.ref->ensureMap();
+      if (!m) {
+        rc[k] = NDTPSO_E_STATE;
+        what[k] = "curvature: no device map";
+        continue;
+      }
+      scans[k].reset(new DeviceScan(r.cur, false, unused, "curvature"));
+      for (int a = 0; a < 3; ++a) poses[3 * k + a] = r.pose[a];
+      ndtpso_map_curvature_job job;
+      std::memset(&job, 0, sizeof(job));
+      job.map = m;
+      job.new_points = scans[k]->pts;
+      job.poses = &poses[3 * k];
+      job.n_poses = 1;
+      job.out = &out[k];
+      jobs.push_back(job);
+      job_req.push_back(k);
+    }
+    if (!jobs.empty()) {
+      const int rc_call = ndtpso_map_curvature_batch(ndtpso_host::device(), jobs.data(), (uint32_t)jobs.size(), nullptr);
+      bool some_job_failed = false;
+      for (const ndtpso_map_curvature_job& job : jobs) some_job_failed = some_job_failed || job.rc != NDTPSO_OK;
+      // (a call refused as a whole failed every request)
+      for (size_t q = 0; q < jobs.size(); ++q) rc[job_req[q]] = (rc_call != NDTPSO_OK && !some_job_failed) ? rc_call : jobs[q].rc;
+    }
+    for (size_t k = 0; k < cnt; ++k) {  // every request's outcome, in request order
+      NDTCurvatureRequest& r = reqs[i + k];
+      if (rc[k] != NDTPSO_OK) {
+        ndtpso_host::check(rc[k], what[k]);
+        r.result = curvature_failed();
+        continue;
+      }
+      r.ref->built = true;
+      r.result = curvature_result(out[k]);
+    }
+    i = j;
+  }
+}
+
 // Several loadLaser() calls (see ndtframe.h): the member's own steps per request, with ONE ndtpso_points_load_scans for a run of
 // requests on per-scan frames.
 void NDTFrame::loadLaserBatch(NDTLoadRequest* reqs, size_t n) {

@@ -502,6 +502,117 @@ _Static_assert(sizeof(ndtpso_search_batch_stats) == NDTPSO_SEARCH_BATCH_STATS_BY
 #endif
 int ndtpso_map_search_batch(ndtpso_ctx *ctx, ndtpso_map_search_job *jobs, uint32_t n_jobs, int score_mode,
                             ndtpso_search_batch_stats *stats /* may be NULL */);
+
+/* ---- curvature of the score at a pose: gradient, Hessian, pose covariance ------------------------------------------
+ * cost_function (core.cpp:26-48) with NDTCell::normalDistribution (ndtcell.cpp:70-78), differentiated once and twice by the pose
+ * (x, y, theta) of a loaded scan against the map, at n_poses poses (3 doubles each).  The reference has no counterpart: it returns
+ * a pose and a cost and says nothing of how well the pose is constrained.  Per scan point (x, y) that lands in a built cell, with
+ * A = s_inv_covar (row-major a00 a01 a10 a11, not assumed symmetric) and mu the cell's mean, in the reference's operations:
+ *   c, s = cos theta, sin theta;  rx, ry = x c - y s, x s + y c;  q = (rx + tx, ry + ty);  d = q - mu;  Q = (d^T A) d;  e = exp(-Q / 2)
+ *   B = A + A^T:  b00, b01, b11 = 2 a00, a01 + a10, 2 a11;   v = B d
+ *   g = (v0, v1, -ry v0 + rx v1)                                             (dQ / dx, dQ / dy, dQ / dtheta)
+ *   h00, h01, h11 = b00, b01, b11;  h02 = -b00 ry + b01 rx;  h12 = -b01 ry + b11 rx
+ *   h22 = ry^2 b00 - 2 rx ry b01 + rx^2 b11 - (v0 rx + v1 ry)
+ *   cost = -sum e;   gradient_k = sum e g_k / 2;   hessian_kl = sum e (h_kl / 2 - g_k g_l / 4)
+ * Cell membership is held fixed: the score is piecewise smooth, as in every NDT formulation.
+ *   - cost is bit for bit ndtpso_map_cost(map, new_points, pose, 1, NDTPSO_SCORE_F64, ...) on every table plan: the same lookup,
+ *     the same exponential, the terms summed in its order.  Always fp64: there is no score mode.
+ *   - The ten sums are a pure function of (map state, scan points, pose): the same bits whether the pose is alone or at any index
+ *     among many, in this call or in a job of ndtpso_map_curvature_batch, on any grid.  One wave owns a pose from the first
+ *     point to the last; no atomics, no reduction across waves.
+ *   - A point whose e is exactly +0. (outside the frame, in a cell that is not built, or Q beyond the exponential's range) adds
+ *     exactly zero to every sum.  A NaN e (a cell built from coincident points) makes all ten sums NaN.
+ *   - n_hit: the points that landed in a built cell.  path: the table plan, as ndtpso_search_stats.path (0, 1, 4, 5).
+ *   - The map: exactly ndtpso_map_cost's side effects -- a pending speculative build committed, an unbuilt map built, the header
+ *     fetched; synchronous.  An empty scan is no error: all zeros, the cost as ndtpso_map_cost gives it.
+ * Errors: NDTPSO_E_ARG for a null pointer, n_poses == 0 or more than NDTPSO_CURVATURE_MAX_POSES, a scan of another context, a
+ * pose that is not finite; NDTPSO_E_CAPACITY when the plan does not fit, as ndtpso_map_cost says it. */
+typedef struct {
+  double cost;         /* == ndtpso_map_cost(F64) bit for bit */
+  double gradient[3];  /* d cost / d (x, y, theta) */
+  double hessian[6];   /* d2 cost: xx, xy, xth, yy, yth, thth */
+  uint32_t n_points, n_hit;
+  uint32_t path, reserved;
+} ndtpso_curvature;
+#define NDTPSO_CURVATURE_BYTES 96
+#define NDTPSO_CURVATURE_MAX_POSES 65536
+#if defined(__cplusplus)
+static_assert(sizeof(ndtpso_curvature) == NDTPSO_CURVATURE_BYTES, "ndtpso_curvature layout");
+#elif defined(__STDC_VERSION__) && __STDC_VERSION__ >= 201112L
+_Static_assert(sizeof(ndtpso_curvature) == NDTPSO_CURVATURE_BYTES, "ndtpso_curvature layout");
+#endif
+/* (stands for cost_function, core.cpp:26-48, and normalDistribution, ndtcell.cpp:70-78, differentiated; no counterpart) */
+int ndtpso_map_curvature(ndtpso_map *map, ndtpso_points *new_points, const double *poses, uint32_t n_poses,
+                         ndtpso_curvature *out);
+/* Several ndtpso_map_curvature calls of one context in shared launches: the R robots of a fleet, or the top-K hits of a
+ * relocalization told apart by curvature.  cost_function and normalDistribution differentiated, as above; the reference has no
+ * counterpart, so the contract is the single call's: job j's out[0 .. n_poses) is bit for bit what
+ *   ndtpso_map_curvature(jobs[j].map, jobs[j].new_points, jobs[j].poses, jobs[j].n_poses, jobs[j].out)
+ * writes when called alone, and afterwards every map is in the state the single call leaves it in.  Maps and scans may repeat.
+ *   - Every distinct map is prepared once, ahead of the launches (its own build if it needs one; one wait for all the maps'
+ *     headers and the scans' point counts, which the plans are made from).  Then one launch per table plan present in the call
+ *     and one wait for the stream, whatever the number of jobs.
+ *   - Errors.  NDTPSO_E_ARG before anything is enqueued or written for a null pointer (ctx, jobs, a job's map, new_points, poses
+ *     or out), n_jobs == 0, a map or scan of another context, or poses that sum to more than NDTPSO_CURVATURE_MAX_POSES.  A job
+ *     with n_poses == 0 or a pose that is not finite gets NDTPSO_E_ARG in its rc, a job whose plan does not fit
+ *     NDTPSO_E_CAPACITY; the other jobs complete.  Returns NDTPSO_OK if every job's rc is 0, else the first failing job's rc.
+ *   - route: 1 = the shared launches; 0 = ndtpso_map_curvature's own call: a call of one job, and a job that is the only valid
+ *     one of its call.  (Both go through the same kernel: the single call is a table of one job.)
+ * stats (may be NULL), counted on the host, of the shared path only: launches = kernel launches enqueued for the curvatures,
+ * waits = waits for the stream behind them (the preparation of the maps is not counted: neither their builds nor the wait for
+ * their headers); single_jobs = jobs that took route 0. */
+typedef struct {
+  ndtpso_map *map;            /* in: reference frame (may repeat across jobs) */
+  ndtpso_points *new_points;  /* in: loaded scan (may repeat across jobs) */
+  const double *poses;        /* in: n_poses x 3 */
+  uint32_t n_poses;           /* in */
+  int32_t rc;                 /* out: NDTPSO_OK or this job's error */
+  ndtpso_curvature *out;      /* in: room for n_poses records; out: the records */
+  int32_t route;              /* out: 1 = the shared launches, 0 = ndtpso_map_curvature's own call */
+  uint32_t reserved;
+} ndtpso_map_curvature_job;
+typedef struct {
+  uint32_t launches, waits, single_jobs, reserved;
+} ndtpso_curvature_batch_stats;
+#define NDTPSO_MAP_CURVATURE_JOB_BYTES 48
+#define NDTPSO_MAP_CURVATURE_JOB_POSES_OFFSET 16
+#define NDTPSO_MAP_CURVATURE_JOB_RC_OFFSET 28
+#define NDTPSO_MAP_CURVATURE_JOB_OUT_OFFSET 32
+#define NDTPSO_MAP_CURVATURE_JOB_ROUTE_OFFSET 40
+#define NDTPSO_CURVATURE_BATCH_STATS_BYTES 16
+#if defined(__cplusplus)
+static_assert(sizeof(ndtpso_map_curvature_job) == NDTPSO_MAP_CURVATURE_JOB_BYTES, "ndtpso_map_curvature_job layout");
+static_assert(sizeof(ndtpso_curvature_batch_stats) == NDTPSO_CURVATURE_BATCH_STATS_BYTES, "ndtpso_curvature_batch_stats layout");
+#elif defined(__STDC_VERSION__) && __STDC_VERSION__ >= 201112L
+_Static_assert(sizeof(ndtpso_map_curvature_job) == NDTPSO_MAP_CURVATURE_JOB_BYTES, "ndtpso_map_curvature_job layout");
+_Static_assert(sizeof(ndtpso_curvature_batch_stats) == NDTPSO_CURVATURE_BATCH_STATS_BYTES, "ndtpso_curvature_batch_stats layout");
+#endif
+int ndtpso_map_curvature_batch(ndtpso_ctx *ctx, ndtpso_map_curvature_job *jobs, uint32_t n_jobs,
+                               ndtpso_curvature_batch_stats *stats /* may be NULL */);
+/* The pose covariance a curvature stands for: the plain inverse of its Hessian (the standard estimate for NDT: the inverse
+ * Hessian of the score at the optimum; cost_function and normalDistribution differentiated, the reference has no counterpart).
+ * It is a RELATIVE measure: the score has no unit of measurement noise in it, so the caller owns the scale factor for their
+ * sensor; what it tells as it stands is which directions are constrained and how they compare.
+ *   - definite = 1: every entry of the curvature's Hessian is finite and the Hessian is positive definite (its Cholesky factor
+ *     exists); cov is its inverse, symmetric; xy_major >= xy_minor are the eigenvalues of cov's translational 2 x 2 block and
+ *     xy_angle the major axis' direction in (-pi/2, pi/2].
+ *   - definite = 0: a saddle, a pose without overlap (all zeros) or a NaN; cov and the three xy fields are zeros.  No error:
+ *     the call returns NDTPSO_OK.
+ * Host only: no context, no device.  NDTPSO_E_ARG for a null pointer. */
+typedef struct {
+  double cov[9];                        /* inverse of the Hessian, row-major, symmetric; zeros unless definite */
+  double xy_major, xy_minor, xy_angle;  /* of cov's translational block; zeros unless definite */
+  int32_t definite;
+  int32_t reserved;
+} ndtpso_pose_covariance;
+#define NDTPSO_POSE_COVARIANCE_BYTES 104
+#if defined(__cplusplus)
+static_assert(sizeof(ndtpso_pose_covariance) == NDTPSO_POSE_COVARIANCE_BYTES, "ndtpso_pose_covariance layout");
+#elif defined(__STDC_VERSION__) && __STDC_VERSION__ >= 201112L
+_Static_assert(sizeof(ndtpso_pose_covariance) == NDTPSO_POSE_COVARIANCE_BYTES, "ndtpso_pose_covariance layout");
+#endif
+int ndtpso_curvature_covariance(const ndtpso_curvature *c, ndtpso_pose_covariance *out);
+
 int ndtpso_map_get_info(ndtpso_map *map, ndtpso_map_info *info);
 /* created cells in ascending index order (row.reserved = the cell's current window slot) */
 int ndtpso_map_get_cells(ndtpso_map *map, ndtpso_cell_row *rows, uint32_t max_rows, uint32_t *n_rows);

@@ -149,6 +149,34 @@ class SearchBatchStats(C.Structure):
     _fields_ = [("launches", C.c_uint32), ("waits", C.c_uint32), ("single_jobs", C.c_uint32), ("reserved", C.c_uint32)]
 
 
+class Curvature(C.Structure):
+    """ndtpso_curvature (include/ndtpso_hip.h): cost, gradient and Hessian of the score at one pose"""
+    _fields_ = [("cost", C.c_double), ("gradient", C.c_double * 3), ("hessian", C.c_double * 6), ("n_points", C.c_uint32),
+                ("n_hit", C.c_uint32), ("path", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+class MapCurvatureJob(C.Structure):
+    """ndtpso_map_curvature_job (include/ndtpso_hip.h): one list of poses of ndtpso_map_curvature_batch"""
+    _fields_ = [("map", C.c_void_p), ("new_points", C.c_void_p), ("poses", C.POINTER(C.c_double)), ("n_poses", C.c_uint32),
+                ("rc", C.c_int32), ("out", C.POINTER(Curvature)), ("route", C.c_int32), ("reserved", C.c_uint32)]
+
+
+class CurvatureBatchStats(C.Structure):
+    """ndtpso_curvature_batch_stats: what a ndtpso_map_curvature_batch call enqueued and waited for, counted on the host"""
+    _fields_ = [("launches", C.c_uint32), ("waits", C.c_uint32), ("single_jobs", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+class PoseCovariance(C.Structure):
+    """ndtpso_pose_covariance: the inverse Hessian of a curvature and the principal axes of its translational block"""
+    _fields_ = [("cov", C.c_double * 9), ("xy_major", C.c_double), ("xy_minor", C.c_double), ("xy_angle", C.c_double),
+                ("definite", C.c_int32), ("reserved", C.c_int32)]
+
+
+CURVATURE_MAX_POSES = 65536
+CURVATURE_DTYPE = np.dtype([("cost", "<f8"), ("gradient", "<f8", (3,)), ("hessian", "<f8", (6,)), ("n_points", "<u4"),
+                            ("n_hit", "<u4"), ("path", "<u4"), ("reserved", "<u4")])
+assert CURVATURE_DTYPE.itemsize == C.sizeof(Curvature) == 96
+
 SEARCH_MAX_TOP_K = 64
 SEARCH_MAX_CANDIDATES = 4096
 # SearchStats.fell_back (NDTPSO_SEARCH_FELL_*): why SCORE_EXACT swept the lattice in fp64
@@ -181,7 +209,7 @@ EXPORTS = [
     "ndtpso_align_pairs_dev", "ndtpso_align_pairs_footprint", "ndtpso_align_pairs_describe",
     "ndtpso_points_create", "ndtpso_points_destroy", "ndtpso_points_load_scan", "ndtpso_points_set", "ndtpso_points_get",
     "ndtpso_map_create", "ndtpso_map_destroy", "ndtpso_map_reset", "ndtpso_map_clear", "ndtpso_map_mark_unbuilt", "ndtpso_map_insert", "ndtpso_map_insert_host",
-    "ndtpso_map_build", "ndtpso_map_speculate_build", "ndtpso_map_align", "ndtpso_map_cost", "ndtpso_map_search", "ndtpso_map_search_batch", "ndtpso_map_get_info", "ndtpso_map_get_cells", "ndtpso_map_get_points",
+    "ndtpso_map_build", "ndtpso_map_speculate_build", "ndtpso_map_align", "ndtpso_map_cost", "ndtpso_map_search", "ndtpso_map_search_batch", "ndtpso_map_curvature", "ndtpso_map_curvature_batch", "ndtpso_curvature_covariance", "ndtpso_map_get_info", "ndtpso_map_get_cells", "ndtpso_map_get_points",
     "ndtpso_map_get_occupancy", "ndtpso_map_snapshot_size", "ndtpso_map_snapshot", "ndtpso_map_restore", "ndtpso_snapshot_describe",
     "ndtpso_map_align_batch", "ndtpso_points_load_scans", "ndtpso_map_update_batch",
     "ndtpso_shard_group_create", "ndtpso_shard_group_destroy", "ndtpso_shard_group_size", "ndtpso_shard_last_error",
@@ -296,6 +324,9 @@ def load(build_if_missing: bool = True):
     L.ndtpso_map_search.argtypes = [vp, vp, C.POINTER(Lattice), C.c_int, C.POINTER(LatticeHit), C.POINTER(C.c_uint32),
                                     C.POINTER(SearchStats)]
     L.ndtpso_map_search_batch.argtypes = [vp, C.POINTER(MapSearchJob), C.c_uint32, C.c_int, C.POINTER(SearchBatchStats)]
+    L.ndtpso_map_curvature.argtypes = [vp, vp, dp, C.c_uint32, C.POINTER(Curvature)]
+    L.ndtpso_map_curvature_batch.argtypes = [vp, C.POINTER(MapCurvatureJob), C.c_uint32, C.POINTER(CurvatureBatchStats)]
+    L.ndtpso_curvature_covariance.argtypes = [C.POINTER(Curvature), C.POINTER(PoseCovariance)]
     L.ndtpso_map_get_info.argtypes = [vp, C.POINTER(MapInfo)]
     L.ndtpso_map_get_cells.argtypes = [vp, C.POINTER(CellRow), C.c_uint32, up]
     L.ndtpso_map_get_points.argtypes = [vp, C.c_int, dp, C.c_uint64, C.POINTER(C.c_uint64)]
@@ -816,6 +847,55 @@ def search_maps(ctx: "Context", jobs, mode=SCORE_EXACT):
     return out, {f: getattr(bs, f) for f, _ in SearchBatchStats._fields_ if f != "reserved"}
 
 
+def _curvature_dict(rec: np.ndarray) -> dict:
+    """a CURVATURE_DTYPE array as a dict of arrays (copies); "raw" keeps the records' bytes"""
+    d = {k: rec[k].copy() for k in ("cost", "gradient", "hessian", "n_points", "n_hit", "path")}
+    d["raw"] = rec.copy()
+    return d
+
+
+def curvature_maps(ctx: "Context", jobs):
+    """ndtpso_map_curvature_batch: the curvatures of `jobs` -- (ResidentMap, ResidentScan, poses [P, 3]) each, maps and scans free
+    to repeat -- in shared launches.  Returns a list with, per job, (dict as ResidentMap.curvature returns, rc, route) and the batch
+    statistics as a dict (launches, waits, single_jobs).  Raises only for the call's own errors; a job's failure is its rc."""
+    n = len(jobs)
+    arr = (MapCurvatureJob * max(n, 1))()
+    keep = []
+    for j, (m, scan, poses) in zip(arr, jobs):
+        poses = _f64(poses).reshape(-1, 3)
+        rec = np.zeros(max(poses.shape[0], 1), dtype=CURVATURE_DTYPE)
+        keep.append((poses, rec))
+        j.map, j.new_points = m._h, scan._h
+        j.poses = _p(poses, C.c_double) if poses.shape[0] else C.cast(rec.ctypes.data, C.POINTER(C.c_double))
+        j.n_poses = poses.shape[0]
+        j.out = C.cast(rec.ctypes.data, C.POINTER(Curvature))
+    bs = CurvatureBatchStats()
+    rc = ctx._lib.ndtpso_map_curvature_batch(ctx._h, arr, n, C.byref(bs))
+    rcs = [j.rc for j in arr[:n]]
+    if rc != OK and not any(r != OK for r in rcs):
+        ctx._chk(rc)
+    out = [(_curvature_dict(rec[:poses.shape[0]]), j.rc, j.route) for j, (poses, rec) in zip(arr[:n], keep)]
+    return out, {f: getattr(bs, f) for f, _ in CurvatureBatchStats._fields_ if f != "reserved"}
+
+
+def curvature_covariance(c) -> dict:
+    """ndtpso_curvature_covariance: the pose covariance (inverse Hessian; a relative measure, the caller owns the scale) of one
+    curvature -- a Curvature, one CURVATURE_DTYPE record, or a dict with "hessian" (6 values: xx, xy, xth, yy, yth, thth).
+    Host only: needs no Context.  Returns cov [3, 3], xy_major, xy_minor, xy_angle, definite."""
+    if isinstance(c, Curvature):
+        cv = c
+    else:
+        cv = Curvature()
+        h = np.asarray(c["hessian"], dtype=np.float64).reshape(6)
+        cv.hessian[:] = [float(v) for v in h]
+    pc = PoseCovariance()
+    rc = load().ndtpso_curvature_covariance(C.byref(cv), C.byref(pc))
+    if rc != OK:
+        raise NdtpsoError(rc, "ndtpso_curvature_covariance")
+    return dict(cov=np.array(pc.cov[:]).reshape(3, 3), xy_major=pc.xy_major, xy_minor=pc.xy_minor, xy_angle=pc.xy_angle,
+                definite=bool(pc.definite))
+
+
 class ResidentScan:
     """ndtpso_points: a loaded scan that stays on the device (the node's one-cell per-scan frame)."""
 
@@ -954,6 +1034,15 @@ class ResidentMap:
         self._ctx._chk(self._lib.ndtpso_map_cost(self._h, scan._h, _p(poses, C.c_double), poses.shape[0], mode,
                                                  _p(costs, C.c_double)))
         return costs
+
+    def curvature(self, scan: ResidentScan, poses) -> dict:
+        """ndtpso_map_curvature: cost, gradient [P, 3] and Hessian [P, 6] (xx, xy, xth, yy, yth, thth) of the score at every pose,
+        always in fp64, with n_points, n_hit and path; "raw" holds the P records as CURVATURE_DTYPE (96 bytes each)."""
+        poses = _f64(poses).reshape(-1, 3)
+        rec = np.zeros(max(poses.shape[0], 1), dtype=CURVATURE_DTYPE)
+        self._ctx._chk(self._lib.ndtpso_map_curvature(self._h, scan._h, _p(poses, C.c_double), poses.shape[0],
+                                                      C.cast(rec.ctypes.data, C.POINTER(Curvature))))
+        return _curvature_dict(rec[:poses.shape[0]])
 
     def search(self, scan: ResidentScan, origin, step, count, top_k, mode=SCORE_EXACT):
         """ndtpso_map_search: the best top_k nodes of the pose lattice (lattice_poses(origin, step, count)) ->

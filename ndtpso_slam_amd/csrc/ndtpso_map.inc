@@ -24,6 +24,7 @@
 #include "ndtpso_map_search.h"
 #include "ndtpso_map_search_jobs.h"
 #include "ndtpso_map_snapshot.h"
+#include "ndtpso_map_curvature.h"
 
 // ---- the kernels of the single calls: one map (or one scan) each, the bodies in ndtpso_map_device.inc ---------------------
 __global__ void __launch_bounds__(kInsertThreads)
@@ -928,6 +929,7 @@ int ndtpso_map_cost(ndtpso_map* m, ndtpso_points* pts, const double* poses, uint
 
 #include "ndtpso_map_search.inc"
 #include "ndtpso_map_search_batch.inc"
+#include "ndtpso_map_curvature.inc"
 
 extern "C" {
 
