@@ -190,6 +190,28 @@ class NDTFrame {
   // of the calling thread's device context go out as ONE ndtpso_map_curvature_batch.  Maps and scans may repeat freely (nothing
   // depends on an earlier result); a request that cannot join takes the member call, in its place.
   static void curvatureBatch(NDTCurvatureRequest* reqs, size_t n);
+  // Free space (not in the reference, whose occupancy grid knows occupied and nothing else): every beam of new_frame's scan,
+  // taken at `pose` (the convention of align()'s result and update()'s argument), is walked from the sensor to its end point
+  // through this frame's occupancy grid on the device (ndtpso_map_trace, include/ndtpso_hip.h); the cells it crosses count as
+  // seen through, its last cell as hit.  Only enqueued, as update() is.  An observer: it draws nothing from std::rand(), leaves
+  // the tracking state, `built`, lastAlignOk() and a pending speculative build as they are, and no later align / cost / update
+  // changes by a bit.  Refused, with the error recorded (ndtpso_slam/status.h) as save() records its refusals: a frame that is
+  // not resident (NDTPSO_RESIDENT=0, 2^21 cells or more), a one-cell per-scan frame, a frame without an occupancy grid or
+  // with one that is not square.
+  void traceFreeSpace(const Vector3d& pose, const NDTFrame* new_frame);
+  // update(trans, new_frame) then also traces the same scan at `trans`: one more launch on the same stream.  updateBatch traces
+  // the flagged frames of a shared run through ONE ndtpso_map_trace_batch behind the shared update launches (so a run's trace
+  // errors, if any, are recorded behind ALL its update errors, where the member calls would record update k, trace k, update k + 1:
+  // the count is the same, the last error may be another).
+  void setTraceOnUpdate(bool on) { s_trace_on_update = on; }
+  bool traceOnUpdate() const { return s_trace_on_update; }
+  // The three-state grid a planner wants, as nav_msgs/OccupancyGrid counts: -1 unknown, 0 .. 100 occupied, og[x + height * y] as
+  // occupancyGrid() stores it -- the reference's value where that is > 0, else the share of the beams that ended in the cell
+  // (0: only ever seen through).  Formed on the device (ndtpso_map_get_nav_grid); settles the frame as occupancyGrid() does.
+  // false, with the error recorded, where traceFreeSpace() refuses.
+  bool navGrid(std::vector<int8_t>& grid, unsigned& og_width, unsigned& og_height);
+  // the raw counters behind it, addressed alike (ndtpso_map_get_trace): beams that ended in the cell, beams that went through
+  bool traceCounts(std::vector<uint32_t>& hits, std::vector<uint64_t>& passes);
   // Several loadLaser() / update() calls at once: observably identical to the member calls in request order -- `built`, the
   // refusal of an update() after a failed align() with its count (updatesRefused()) and recorded error, the rule for the
   // speculative build, every error recorded as the member call records it -- but consecutive requests that qualify share their
@@ -260,6 +282,9 @@ class NDTFrame {
   std::vector<uint32_t> s_created;  // indices of created cells, in creation order
   bool s_table_dirty{true};         // the device reference table must be re-uploaded before the next align
   bool s_last_align_ok{true};
+  bool s_trace_on_update{false};
+  const char* traceRefusal() const;        // why this frame cannot be traced (not resident, a one-cell scan frame), or nullptr
+  ndtpso_map* traceMap(const char* what);  // the map traceFreeSpace / navGrid work on, or nullptr with the refusal recorded
   void append(const double* xy, const int32_t* idx, uint32_t n);
   bool uploadTable();  // false: the device refused the table (error recorded, see status.h)
   // what align() does around its alignment, step by step (alignBatch does the same steps around a shared launch)

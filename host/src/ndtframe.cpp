@@ -274,10 +274,11 @@ void NDTFrame::update(Vector3d trans, NDTFrame* const new_frame) {
     const double pose[3] = {trans.x(), trans.y(), trans.z()};
     ndtpso_map* m = ensureMap();
     if (!ndtpso_host::check(ndtpso_map_mark_unbuilt(m), "update")) return;  // ndtframe.cpp:188, also when no point follows
-    if (!is_foreign && new_frame->s_resident && new_frame->d_scan_ && !new_frame->d_map_) {  // device to device, nothing to wait for
+    std::vector<double> pts;
+    const bool on_device = !is_foreign && new_frame->s_resident && new_frame->d_scan_ && !new_frame->d_map_;
+    if (on_device) {  // device to device, nothing to wait for
       if (!ndtpso_host::check(ndtpso_map_insert(m, new_frame->d_scan_, pose), "update")) return;
     } else {
-      std::vector<double> pts;
       if (is_foreign) pts.swap(foreign); else new_frame->collectPoints(pts);
       if (!ndtpso_host::check(ndtpso_map_insert_host(m, pts.data(), (uint32_t)(pts.size() / 2), pose), "update")) return;
     }
@@ -285,8 +286,22 @@ void NDTFrame::update(Vector3d trans, NDTFrame* const new_frame) {
     // critical path; should something other than align / build come first, the device takes the build back
     // (ndtpso_map_speculate_build), so the lazy build of the reference is what every caller still observes.
     if (s_iter > 0 && speculate_after_update()) ndtpso_host::check(ndtpso_map_speculate_build(m), "update");
+    if (s_trace_on_update && traceRefusal()) {  // (as traceFreeSpace refuses)
+      ndtpso_host::check(NDTPSO_E_STATE, (std::string("update: trace: ") + traceRefusal()).c_str());
+    } else if (s_trace_on_update) {  // the same scan at the same pose through the occupancy grid (setTraceOnUpdate), behind the build
+      if (on_device) {
+        ndtpso_host::check(ndtpso_map_trace(m, new_frame->d_scan_, pose), "update: trace");
+      } else {
+        const uint32_t cap = std::max(kScanCapacity, (uint32_t)(pts.size() / 2));
+        ndtpso_points* tmp = ndtpso_host::acquire_scan(cap);
+        if (ndtpso_host::check(ndtpso_points_set(tmp, pts.data(), (uint32_t)(pts.size() / 2)), "update: trace"))
+          ndtpso_host::check(ndtpso_map_trace(m, tmp, pose), "update: trace");
+        ndtpso_host::release_scan(tmp, cap);
+      }
+    }
     return;
   }
+  if (s_trace_on_update) ndtpso_host::check(NDTPSO_E_STATE, (std::string("update: trace: ") + traceRefusal()).c_str());  // (as traceFreeSpace refuses)
   std::vector<double> xy;
   if (is_foreign) xy.swap(foreign); else new_frame->collectPoints(xy);
   const uint32_t n = (uint32_t)(xy.size() / 2);
@@ -1051,6 +1066,76 @@ void NDTFrame::curvatureBatch(NDTCurvatureRequest* reqs, size_t n) {
   }
 }
 
+// ---- free space (see ndtframe.h): ndtpso_map_trace / ndtpso_map_get_nav_grid of the frame's device map ---------------------------
+const char* NDTFrame::traceRefusal() const {
+  if (!s_resident) return numOfCells >= (1u << 21) ? "a frame of 2^21 cells or more is kept on the host's side" : "the frame is not resident";
+  if (numOfCells == 1 || (d_scan_ && !d_map_)) return "a one-cell scan frame holds no map";
+  return nullptr;
+}
+
+ndtpso_map* NDTFrame::traceMap(const char* what) {
+  auto refused = [&](const char* why) -> ndtpso_map* {
+    ndtpso_host::check(NDTPSO_E_STATE, (std::string(what) + ": " + why).c_str());
+    return nullptr;
+  };
+  if (const char* why = traceRefusal()) return refused(why);
+  ndtpso_map* m = ensureMap();
+  return m ? m : refused("no device map");
+}
+
+void NDTFrame::traceFreeSpace(const Vector3d& pose, const NDTFrame* new_frame) {
+  if (!new_frame) {
+    ndtpso_host::check(NDTPSO_E_ARG, "traceFreeSpace: null argument");
+    return;
+  }
+  std::vector<double> foreign;
+  const bool is_foreign = new_frame->dev() != dev();
+  if (is_foreign && s_resident) new_frame->collectPoints(foreign);
+  ndtpso_host::Use use(dev());
+  ndtpso_map* m = traceMap("traceFreeSpace");
+  if (!m) return;
+  const DeviceScan scan(new_frame, is_foreign, foreign, "traceFreeSpace");
+  const double p[3] = {pose.x(), pose.y(), pose.z()};
+  ndtpso_host::check(ndtpso_map_trace(m, scan.pts, p), "traceFreeSpace");
+}
+
+bool NDTFrame::navGrid(std::vector<int8_t>& grid, unsigned& og_width, unsigned& og_height) {
+  grid.clear();
+  og_width = og_height = 0;
+  ndtpso_host::Use use(dev());
+  ndtpso_map* m = traceMap("navGrid");
+  if (!m) return false;
+  ndtpso_trace_info info;
+  if (!ndtpso_host::check(ndtpso_map_get_trace_info(m, &info), "navGrid")) return false;
+  grid.assign((size_t)info.width * info.height, (int8_t)-1);
+  if (!ndtpso_host::check(ndtpso_map_get_nav_grid(m, grid.data(), grid.size()), "navGrid")) {
+    grid.clear();
+    return false;
+  }
+  og_width = info.width;
+  og_height = info.height;
+  return true;
+}
+
+bool NDTFrame::traceCounts(std::vector<uint32_t>& hits, std::vector<uint64_t>& passes) {
+  hits.clear();
+  passes.clear();
+  ndtpso_host::Use use(dev());
+  ndtpso_map* m = traceMap("traceCounts");
+  if (!m) return false;
+  ndtpso_trace_info info;
+  if (!ndtpso_host::check(ndtpso_map_get_trace_info(m, &info), "traceCounts")) return false;
+  const size_t n = (size_t)info.width * info.height;
+  hits.assign(n, 0u);
+  passes.assign(n, 0ull);
+  if (!ndtpso_host::check(ndtpso_map_get_trace(m, hits.data(), passes.data(), n), "traceCounts")) {
+    hits.clear();
+    passes.clear();
+    return false;
+  }
+  return true;
+}
+
 // Several loadLaser() calls (see ndtframe.h): the member's own steps per request, with ONE ndtpso_points_load_scans for a run of
 // requests on per-scan frames.
 void NDTFrame::loadLaserBatch(NDTLoadRequest* reqs, size_t n) {
@@ -1189,6 +1274,30 @@ void NDTFrame::updateBatch(NDTUpdateRequest* reqs, size_t n) {
         ndtpso_host::check(ndtpso_map_mark_unbuilt(nullptr), "update");
       else
         ndtpso_host::check((rc_call != NDTPSO_OK && !some_job_failed) ? rc_call : jobs[(size_t)w].rc, "update");
+    }
+    // the flagged frames' scans through their occupancy grids (setTraceOnUpdate): ONE launch behind the shared update launches
+    std::vector<ndtpso_map_trace_job> traces;
+    for (size_t k = i; k < j; ++k) {
+      const int w = what[k - i];
+      if (w < 0 || !reqs[k].frame->s_trace_on_update) continue;
+      if (const char* why = reqs[k].frame->traceRefusal()) {
+        ndtpso_host::check(NDTPSO_E_STATE, (std::string("update: trace: ") + why).c_str());
+        continue;
+      }
+      if (((rc_call != NDTPSO_OK && !some_job_failed) ? rc_call : jobs[(size_t)w].rc) != NDTPSO_OK) continue;  // (update() returns before its trace)
+      ndtpso_map_trace_job t;
+      std::memset(&t, 0, sizeof(t));
+      t.map = jobs[(size_t)w].map;
+      t.points = jobs[(size_t)w].points;
+      std::memcpy(t.pose, jobs[(size_t)w].pose, sizeof(t.pose));
+      traces.push_back(t);
+    }
+    if (!traces.empty()) {
+      const int rc_trace = ndtpso_map_trace_batch(ndtpso_host::device(), traces.data(), (uint32_t)traces.size());
+      bool some_trace_failed = false;
+      for (const ndtpso_map_trace_job& t : traces) some_trace_failed = some_trace_failed || t.rc != NDTPSO_OK;
+      for (const ndtpso_map_trace_job& t : traces)
+        ndtpso_host::check((rc_trace != NDTPSO_OK && !some_trace_failed) ? rc_trace : t.rc, "update: trace");
     }
     i = j;
   }

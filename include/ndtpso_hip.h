@@ -623,6 +623,95 @@ int ndtpso_map_get_points(ndtpso_map *map, int slot0_only, double *xy, uint64_t 
 int ndtpso_map_get_occupancy(ndtpso_map *map, int8_t *og, uint64_t og_bytes, uint32_t *og_width, uint32_t *og_height,
                              uint32_t extent[4]);
 
+/* ---- free space: every beam of a scan traced through the occupancy grid --------------------------------------------
+ * The reference has no counterpart: its occupancy grid (ndtframe.cpp:79-112) holds int8(100 * normalDistribution) where a built
+ * cell's Gaussian was rasterised and 0 everywhere else, so "never seen" and "seen through, nothing there" are the same entry.
+ * Tracing keeps, per entry of that same grid, how many beams ended there (hits, uint32) and how many went through (passes,
+ * uint64: the origin's cell takes every beam of every scan).
+ *   The grid is the map's occupancy grid: og_width = ceil(width / og_cell_size), og_height likewise; cell (ox, oy) of a point q
+ *   is ox = floor((q.x + width / 2.) / og_cell_size), oy likewise (getCellIndex's arithmetic, ndtframe.cpp:240-249: true
+ *   division); the entry is at = ox + og_height * oy, as ndtpso_map_get_occupancy addresses it, so the grids overlay entry for
+ *   entry.  With og_width != og_height that addressing makes distinct cells collide (the reference's quirk): NDTPSO_E_ARG.
+ *   One quirk of the reference is kept: for the last double below the bound fl(q.x + width / 2.) == width, so ox == og_width (oy
+ *   likewise).  Such a cell is addressed like any other: with oy < og_height - 1 its entry is (0, oy + 1)'s -- the wrap into the
+ *   next row that the reference's own linear index makes (getCellIndex) -- and is counted there, the extent's max ox becomes
+ *   og_width; an entry at or beyond og_width * og_height is counted in the totals and the extent and not written.  This
+ *   concerns rays that end (or start) within one ulp of the frame's upper bound.
+ *   One ray per point p of the scan: from o = (pose[0], pose[1]) to e = (x c - y s + pose[0], x s + y c + pose[1]) with
+ *   (c, s) = the DEVICE's sincos of pose[2] (ndtpso_device_math kind 2), no fused operations.  A ray whose origin or end is not
+ *   strictly inside the frame (|q.x| < width / 2, |q.y| < height / 2) is skipped and counted in n_skipped.
+ *   The traversal, in plain IEEE fp64 (hw = width / 2., cs = og_cell_size):
+ *     fx0 = (o.x + hw) / cs, fy0 likewise;  fx1 = (e.x + hw) / cs, fy1 likewise
+ *     ix, iy = floor(fx0), floor(fy0);  jx, jy = floor(fx1), floor(fy1);  dx, dy = fx1 - fx0, fy1 - fy0
+ *     sx = jx > ix ? 1 : -1, sy likewise;  nx = |jx - ix|, ny = |jy - iy|
+ *     tdx = nx ? 1. / |dx| : inf;  tx0 = nx ? ((sx > 0 ? ix + 1 : ix) - fx0) / dx : inf   (y likewise)
+ *     x-crossing i (0 <= i < nx) is at tx_i = tx0 + (double)i * tdx, y-crossing j at ty_j = ty0 + (double)j * tdy
+ *   The visited cells are the staircase from (ix, iy) to (jx, jy) that merges the two crossing sequences: x-crossing i goes
+ *   before y-crossing j iff tx_i <= ty_j (a tie steps x first); an axis whose crossings are used up no longer competes.  A ray
+ *   visits exactly nx + ny + 1 distinct cells and ends in (jx, jy).  Every visited cell but the last gets passes += 1, the last
+ *   gets hits += 1.  The adds are integer atomics: the counters are a pure function of the multiset of (scan, pose) traced,
+ *   whatever the order of the calls, alone or in a batch.
+ * ndtpso_map_trace only enqueues on the context's stream, as ndtpso_map_insert does.  It is an observer: it reads nothing of the
+ * cells, writes nothing but its own buffers, neither settles nor disturbs a pending speculative build, and no later align, cost,
+ * search, curvature, export or snapshot changes by a bit.  The counters are allocated and zeroed at a map's first trace; a map
+ * that is never traced pays nothing.  An empty scan is no error.  ndtpso_map_clear zeroes counters and totals, ndtpso_map_reset
+ * keeps them, ndtpso_map_destroy frees them.  Snapshot format 1 does not carry them: a restored map starts with none.
+ * Errors: NDTPSO_E_ARG for a null pointer (pose is required), a pose that is not finite, a scan of another context, a grid that
+ * is not square; NDTPSO_E_STATE for a map without an occupancy grid (og_cell_size 0).  Out of scope: beams without a return,
+ * per-scan de-duplication, decay, clipping of rays that leave the frame. */
+int ndtpso_map_trace(ndtpso_map *map, const ndtpso_points *points, const double pose[3]);
+/* Several ndtpso_map_trace calls of one context -- several robots' scans, or several scans of one map -- in ONE launch, whatever
+ * n_jobs (the reference has no counterpart).  Maps and scans may repeat; nothing needs ordering because the adds commute, and
+ * every map's counters are what the single calls give.  NDTPSO_E_ARG before anything is enqueued or written for a null pointer
+ * (ctx, jobs, a job's map or points), n_jobs == 0, or a map or scan of another context.  A job whose own map or pose
+ * ndtpso_map_trace would refuse carries that error in its rc and the other jobs complete.  Returns NDTPSO_OK, or the first
+ * failing job's rc. */
+typedef struct {
+  ndtpso_map *map;             /* in (may repeat across jobs) */
+  const ndtpso_points *points; /* in: loaded scan (may repeat across jobs) */
+  double pose[3];              /* in */
+  int32_t rc;                  /* out: NDTPSO_OK or this job's error */
+  uint32_t reserved;
+} ndtpso_map_trace_job;
+#define NDTPSO_MAP_TRACE_JOB_BYTES 48
+#define NDTPSO_MAP_TRACE_JOB_POSE_OFFSET 16
+#define NDTPSO_MAP_TRACE_JOB_RC_OFFSET 40
+int ndtpso_map_trace_batch(ndtpso_ctx *ctx, ndtpso_map_trace_job *jobs, uint32_t n_jobs);
+/* What has been traced since the last clear (the reference has no counterpart).  allocated: the map has counters (0: never
+ * traced; everything else but width and height is then as of an untraced map).  extent = {min ox, max ox, min oy, max oy} of the
+ * cells with any count, kept by device-side min / max as the occupancy extents are ({UINT32_MAX, 0, UINT32_MAX, 0}: none).
+ * n_rays: rays traced; n_skipped: rays skipped at the frame's bound; n_steps: the sum of nx + ny == the sum of passes.
+ * Synchronous. */
+typedef struct {
+  uint32_t allocated, width, height, reserved;
+  uint32_t extent[4];
+  uint64_t n_rays, n_skipped, n_steps;
+} ndtpso_trace_info;
+#define NDTPSO_TRACE_INFO_BYTES 56
+#define NDTPSO_TRACE_INFO_EXTENT_OFFSET 16
+#define NDTPSO_TRACE_INFO_N_RAYS_OFFSET 32
+#if defined(__cplusplus)
+static_assert(sizeof(ndtpso_map_trace_job) == NDTPSO_MAP_TRACE_JOB_BYTES, "ndtpso_map_trace_job layout");
+static_assert(sizeof(ndtpso_trace_info) == NDTPSO_TRACE_INFO_BYTES, "ndtpso_trace_info layout");
+#elif defined(__STDC_VERSION__) && __STDC_VERSION__ >= 201112L
+_Static_assert(sizeof(ndtpso_map_trace_job) == NDTPSO_MAP_TRACE_JOB_BYTES, "ndtpso_map_trace_job layout");
+_Static_assert(sizeof(ndtpso_trace_info) == NDTPSO_TRACE_INFO_BYTES, "ndtpso_trace_info layout");
+#endif
+int ndtpso_map_get_trace_info(ndtpso_map *map, ndtpso_trace_info *info);
+/* The raw counters, og_width * og_height entries each, addressed as the occupancy grid is (the reference has no counterpart).
+ * Either pointer may be NULL; capacity_entries too small: NDTPSO_E_ARG.  Of a map never traced: zeros.  Synchronous. */
+int ndtpso_map_get_trace(ndtpso_map *map, uint32_t *hits, uint64_t *passes, uint64_t capacity_entries);
+/* The three-state grid a planner wants (nav_msgs/OccupancyGrid's convention; the reference has no counterpart), formed on the
+ * device from the occupancy keys and the counters, one byte per entry across the host link.  Settles the map exactly as
+ * ndtpso_map_get_occupancy does.  Per entry, with v the byte ndtpso_map_get_occupancy returns, h = hits, p = passes:
+ *   v > 0       -> v: the reference's word stands
+ *   h + p == 0  -> -1: unknown
+ *   else        -> (100 * h + (h + p) / 2) / (h + p) in unsigned 64-bit integer arithmetic: 0 for a cell only ever seen through
+ * (v is never negative -- the reference's grid starts as zeros and int8(100 * p) of a Gaussian is 0 .. 100 --, and its own
+ * picture draws og > 0 only, ndtframe.cpp:408: a 0 of the reference says nothing, so the counters speak there.)
+ * NDTPSO_E_STATE without an occupancy grid, NDTPSO_E_ARG for a null pointer or fewer than og_width * og_height bytes. */
+int ndtpso_map_get_nav_grid(ndtpso_map *map, int8_t *grid, uint64_t bytes);
+
 /* ---- a resident map saved to a blob and restored bit for bit ---------------------------------------------------
  * The reference has no counterpart (dumpMap, ndtframe.cpp:314-328, writes points for a plot; nothing reads them back).  A
  * snapshot is a compact, deterministic, versioned image of everything about a map that is primary state: the created cells in
@@ -636,7 +725,9 @@ int ndtpso_map_get_occupancy(ndtpso_map *map, int8_t *og, uint64_t og_bytes, uin
  * snapshot(restore(blob)) == blob.  Size is proportional to content, never to the frame:
  *   bytes <= 4096 + 192 * n_created + 80 * n_slots_used + 528 * n_chunks + 8 * og_box_entries.
  * Format 1: little-endian, 16-byte aligned sections, 64-bit sizes and offsets, magic, version, the constants it was made with
- * (NDTPSO_WINDOW_SIZE, NDTPSO_MAX_POINTS_PER_CELL, chunk size, cell record size), FNV-1a checksums of header and body. */
+ * (NDTPSO_WINDOW_SIZE, NDTPSO_MAX_POINTS_PER_CELL, chunk size, cell record size), FNV-1a checksums of header and body.
+ * Format 1 does not carry the free-space counters of ndtpso_map_trace (they are evidence about the world, not state any
+ * alignment depends on): a restored map starts with none.  A format 2 that does is a follow-up. */
 typedef struct {
   uint32_t version, n_created, n_built, built; /* format; created cells; cells of the table (0 unless built); NDTFrame::built */
   uint64_t n_slots_used, n_chunks, n_points_stored, og_box_entries, bytes;

@@ -172,6 +172,17 @@ class PoseCovariance(C.Structure):
                 ("definite", C.c_int32), ("reserved", C.c_int32)]
 
 
+class MapTraceJob(C.Structure):
+    """ndtpso_map_trace_job (include/ndtpso_hip.h): one scan traced through one map's occupancy grid"""
+    _fields_ = [("map", C.c_void_p), ("points", C.c_void_p), ("pose", C.c_double * 3), ("rc", C.c_int32), ("reserved", C.c_uint32)]
+
+
+class TraceInfo(C.Structure):
+    """ndtpso_trace_info: what has been traced into a map since its last clear"""
+    _fields_ = [("allocated", C.c_uint32), ("width", C.c_uint32), ("height", C.c_uint32), ("reserved", C.c_uint32),
+                ("extent", C.c_uint32 * 4), ("n_rays", C.c_uint64), ("n_skipped", C.c_uint64), ("n_steps", C.c_uint64)]
+
+
 CURVATURE_MAX_POSES = 65536
 CURVATURE_DTYPE = np.dtype([("cost", "<f8"), ("gradient", "<f8", (3,)), ("hessian", "<f8", (6,)), ("n_points", "<u4"),
                             ("n_hit", "<u4"), ("path", "<u4"), ("reserved", "<u4")])
@@ -209,7 +220,8 @@ EXPORTS = [
     "ndtpso_align_pairs_dev", "ndtpso_align_pairs_footprint", "ndtpso_align_pairs_describe",
     "ndtpso_points_create", "ndtpso_points_destroy", "ndtpso_points_load_scan", "ndtpso_points_set", "ndtpso_points_get",
     "ndtpso_map_create", "ndtpso_map_destroy", "ndtpso_map_reset", "ndtpso_map_clear", "ndtpso_map_mark_unbuilt", "ndtpso_map_insert", "ndtpso_map_insert_host",
-    "ndtpso_map_build", "ndtpso_map_speculate_build", "ndtpso_map_align", "ndtpso_map_cost", "ndtpso_map_search", "ndtpso_map_search_batch", "ndtpso_map_curvature", "ndtpso_map_curvature_batch", "ndtpso_curvature_covariance", "ndtpso_map_get_info", "ndtpso_map_get_cells", "ndtpso_map_get_points",
+    "ndtpso_map_build", "ndtpso_map_speculate_build", "ndtpso_map_align", "ndtpso_map_cost", "ndtpso_map_search", "ndtpso_map_search_batch", "ndtpso_map_curvature", "ndtpso_map_curvature_batch", "ndtpso_curvature_covariance",
+    "ndtpso_map_trace", "ndtpso_map_trace_batch", "ndtpso_map_get_trace_info", "ndtpso_map_get_trace", "ndtpso_map_get_nav_grid", "ndtpso_map_get_info", "ndtpso_map_get_cells", "ndtpso_map_get_points",
     "ndtpso_map_get_occupancy", "ndtpso_map_snapshot_size", "ndtpso_map_snapshot", "ndtpso_map_restore", "ndtpso_snapshot_describe",
     "ndtpso_map_align_batch", "ndtpso_points_load_scans", "ndtpso_map_update_batch",
     "ndtpso_shard_group_create", "ndtpso_shard_group_destroy", "ndtpso_shard_group_size", "ndtpso_shard_last_error",
@@ -327,6 +339,11 @@ def load(build_if_missing: bool = True):
     L.ndtpso_map_curvature.argtypes = [vp, vp, dp, C.c_uint32, C.POINTER(Curvature)]
     L.ndtpso_map_curvature_batch.argtypes = [vp, C.POINTER(MapCurvatureJob), C.c_uint32, C.POINTER(CurvatureBatchStats)]
     L.ndtpso_curvature_covariance.argtypes = [C.POINTER(Curvature), C.POINTER(PoseCovariance)]
+    L.ndtpso_map_trace.argtypes = [vp, vp, dp]
+    L.ndtpso_map_trace_batch.argtypes = [vp, C.POINTER(MapTraceJob), C.c_uint32]
+    L.ndtpso_map_get_trace_info.argtypes = [vp, C.POINTER(TraceInfo)]
+    L.ndtpso_map_get_trace.argtypes = [vp, C.POINTER(C.c_uint32), C.POINTER(C.c_uint64), C.c_uint64]
+    L.ndtpso_map_get_nav_grid.argtypes = [vp, C.POINTER(C.c_int8), C.c_uint64]
     L.ndtpso_map_get_info.argtypes = [vp, C.POINTER(MapInfo)]
     L.ndtpso_map_get_cells.argtypes = [vp, C.POINTER(CellRow), C.c_uint32, up]
     L.ndtpso_map_get_points.argtypes = [vp, C.c_int, dp, C.c_uint64, C.POINTER(C.c_uint64)]
@@ -896,6 +913,22 @@ def curvature_covariance(c) -> dict:
                 definite=bool(pc.definite))
 
 
+def trace_maps(ctx: "Context", jobs):
+    """ndtpso_map_trace_batch: the traces of `jobs` -- (ResidentMap, ResidentScan, pose) each, maps and scans free to repeat -- in
+    ONE launch.  Returns the jobs' rcs.  Raises only for the call's own errors; a job's failure is its rc."""
+    n = len(jobs)
+    arr = (MapTraceJob * max(n, 1))()
+    for j, (m, scan, pose) in zip(arr, jobs):
+        j.map, j.points = m._h, scan._h
+        j.pose[:] = [float(v) for v in _f64(pose, 3)]
+        j.rc = OK
+    rc = ctx._lib.ndtpso_map_trace_batch(ctx._h, arr, n)
+    rcs = [j.rc for j in arr[:n]]
+    if rc != OK and not any(r != OK for r in rcs):
+        ctx._chk(rc)
+    return rcs
+
+
 class ResidentScan:
     """ndtpso_points: a loaded scan that stays on the device (the node's one-cell per-scan frame)."""
 
@@ -1043,6 +1076,40 @@ class ResidentMap:
         self._ctx._chk(self._lib.ndtpso_map_curvature(self._h, scan._h, _p(poses, C.c_double), poses.shape[0],
                                                       C.cast(rec.ctypes.data, C.POINTER(Curvature))))
         return _curvature_dict(rec[:poses.shape[0]])
+
+    def trace(self, scan: ResidentScan, pose):
+        """ndtpso_map_trace: every beam of the scan, taken at `pose`, walked through the occupancy grid (enqueued, an observer)"""
+        self._ctx._chk(self._lib.ndtpso_map_trace(self._h, scan._h, _p(_f64(pose, 3), C.c_double)))
+
+    def trace_info(self) -> dict:
+        """ndtpso_map_get_trace_info: allocated, width, height, extent (min ox, max ox, min oy, max oy), n_rays, n_skipped, n_steps"""
+        i = TraceInfo()
+        self._ctx._chk(self._lib.ndtpso_map_get_trace_info(self._h, C.byref(i)))
+        return dict(allocated=int(i.allocated), width=int(i.width), height=int(i.height), extent=tuple(int(v) for v in i.extent),
+                    n_rays=int(i.n_rays), n_skipped=int(i.n_skipped), n_steps=int(i.n_steps))
+
+    def _og_shape(self):
+        i = TraceInfo()
+        self._ctx._chk(self._lib.ndtpso_map_get_trace_info(self._h, C.byref(i)))
+        return int(i.width), int(i.height)
+
+    def trace_counts(self):
+        """ndtpso_map_get_trace: (hits [h, w] uint32, passes [h, w] uint64); entry [oy, ox] of a square grid is the occupancy grid's
+        og[ox + h * oy]"""
+        w, h = self._og_shape()
+        hits = np.zeros(max(w * h, 1), dtype=np.uint32)
+        passes = np.zeros(max(w * h, 1), dtype=np.uint64)
+        self._ctx._chk(self._lib.ndtpso_map_get_trace(self._h, hits.ctypes.data_as(C.POINTER(C.c_uint32)),
+                                                      passes.ctypes.data_as(C.POINTER(C.c_uint64)), hits.size))
+        return hits[:w * h].reshape(h, w), passes[:w * h].reshape(h, w)
+
+    def nav_grid(self) -> np.ndarray:
+        """ndtpso_map_get_nav_grid: [h, w] int8 -- the reference's value where that is > 0, else -1 unknown, else the share of the
+        beams that ended in the cell, 0 .. 100 (0: only ever seen through)"""
+        w, h = self._og_shape()
+        g = np.zeros(max(w * h, 1), dtype=np.int8)
+        self._ctx._chk(self._lib.ndtpso_map_get_nav_grid(self._h, g.ctypes.data_as(C.POINTER(C.c_int8)), g.size))
+        return g[:w * h].reshape(h, w)
 
     def search(self, scan: ResidentScan, origin, step, count, top_k, mode=SCORE_EXACT):
         """ndtpso_map_search: the best top_k nodes of the pose lattice (lattice_poses(origin, step, count)) ->

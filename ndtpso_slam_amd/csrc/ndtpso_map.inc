@@ -16,6 +16,7 @@
 //   created[]              indices of created cells (creation order; every per-cell pass runs over this list)
 //   image                  the alignment table (bitmap words + records of the BUILT cells), rebuilt by pack
 //   og_key[]               occupancy grid: (build number, cell, int8 value) keys, atomicMax = "the later write wins"
+//   trace_hits/passes[]    free-space evidence per occupancy entry (ndtpso_map_trace), allocated at the first trace
 
 
 #include "ndtpso_map_device.inc"
@@ -25,6 +26,7 @@
 #include "ndtpso_map_search_jobs.h"
 #include "ndtpso_map_snapshot.h"
 #include "ndtpso_map_curvature.h"
+#include "ndtpso_map_trace.h"
 
 // ---- the kernels of the single calls: one map (or one scan) each, the bodies in ndtpso_map_device.inc ---------------------
 __global__ void __launch_bounds__(kInsertThreads)
@@ -145,6 +147,9 @@ struct ndtpso_map {
   MapP p{};
   DevBuf cell, win_sum, win_cov, win_count, slot_head, slot_tail, slot_len, chunk_pts, chunk_next, free_list, created,
       hdr, image, og_key, stage;
+  // ndtpso_map_trace: hits (uint32) and passes (uint64) per occupancy entry and a TraceTotals, allocated at the first trace; nav:
+  // the staged bytes of ndtpso_map_get_nav_grid
+  DevBuf trace_hits, trace_passes, trace_tot, nav;
   DevBuf snap, snap_idx;       // ndtpso_map_snapshot / ndtpso_map_restore: the staged blob and its index, for the length of a call
   double og_cell_size = 0.;
   uint32_t og_width = 0, og_height = 0, og_count = 0;
@@ -170,10 +175,12 @@ struct ndtpso_map {
 
 namespace {
 
+int trace_zero(ndtpso_map* m);  // (ndtpso_map_trace.inc)
+
 void map_release(ndtpso_map* m) {
   for (DevBuf* b : {&m->cell, &m->win_sum, &m->win_cov, &m->win_count, &m->slot_head, &m->slot_tail, &m->slot_len,
                     &m->chunk_pts, &m->chunk_next, &m->free_list, &m->created, &m->hdr, &m->image, &m->og_key, &m->stage,
-                    &m->undo, &m->snap, &m->snap_idx})
+                    &m->undo, &m->snap, &m->snap_idx, &m->trace_hits, &m->trace_passes, &m->trace_tot, &m->nav})
     b->release();
   if (m->spec_hdr) (void)hipHostFree(m->spec_hdr);
   m->spec_hdr = nullptr;
@@ -194,6 +201,8 @@ int map_clear(ndtpso_map* m) {  // the state of a freshly constructed frame
   m->host_hdr = h;
   HIP_TRY(c, hipMemcpyAsync(m->hdr.p, &m->host_hdr, sizeof(h), hipMemcpyHostToDevice, c->stream));
   if (m->og_count) HIP_TRY(c, hipMemsetAsync(m->og_key.p, 0, (size_t)m->og_count * 8, c->stream));
+  if (m->trace_tot.p)
+    if (int rc = trace_zero(m)) return rc;
   HIP_TRY(c, hipStreamSynchronize(c->stream));
   m->built = false;
   m->spec = false;
@@ -930,6 +939,7 @@ int ndtpso_map_cost(ndtpso_map* m, ndtpso_points* pts, const double* poses, uint
 #include "ndtpso_map_search.inc"
 #include "ndtpso_map_search_batch.inc"
 #include "ndtpso_map_curvature.inc"
+#include "ndtpso_map_trace.inc"
 
 extern "C" {
 
